@@ -6,7 +6,11 @@ python bench.py --gpus N --steps K --warmup W     (N > 1: launched by torch.dist
 A "step" is one forward 2^22-point NTT (natural order in/out, device resident, synthetic uniform
 coefficients).  With N ranks every rank transforms its own polynomials (the path shards by
 polynomial, no data-path collective): weak scaling, value = N*K / max-over-ranks time.
-Prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line.  A plain run sets up, warms up, times exactly K steps in one region and prints the line; --full adds
+the oracle check of the timed plans, the median of --samples regions (default 5), the warm and one-at-a-time regimes,
+per-pass times, the counter-based roofline and the `cpu_baseline` object.  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (float64, one row per element: low and high 32 bits, exact), a seeded sample of at most
+2^21 elements per output with its indices in DIR/<name>_index.npy.
 Other workloads (--workload): batch16 (1024 x 2^16), mul22 (polynomial multiply, NTT size 2^22),
 roundtrip16 (fwd+inv 2^16), fourstep (sharded four-step NTT with an RCCL all-to-all, N >= 1),
 open22 (kzg::open's quotient: 2^22 coefficients / (x - z)), eval22 (Polynomial::evaluate, 2^22 coefficients),
@@ -60,6 +64,35 @@ def synth(n, seed):
         x[bad] = rng.integers(0, top, size=int(bad.sum()), dtype=np.uint64)
         bad = x >= P
     return x
+
+
+DUMP_MAX_ELEMENTS = 1 << 21    # per run: 2^21 x (16 bytes of value + 8 of index) = 48 MiB at most
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: `outputs` maps a name to a flat tensor or array of field elements (64-bit).  Each goes to
+    DIR/<name>.npy as float64 rows [low 32 bits, high 32 bits] (exact); an output longer than its share of DUMP_MAX_ELEMENTS
+    is replaced by a seeded stratified sample (one random element per stride), whose indices go to DIR/<name>_index.npy"""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_MAX_ELEMENTS // len(outputs)
+    for k, (name, t) in enumerate(sorted(outputs.items())):
+        size = t.numel() if hasattr(t, "numel") else t.size
+        idx = None
+        if size > share:
+            stride = -(-size // share)
+            rng = np.random.default_rng(0x5EEDD000 + k)
+            idx = np.arange(0, size, stride, dtype=np.int64)
+            idx = np.minimum(idx + rng.integers(0, stride, size=idx.size), size - 1)
+            if hasattr(t, "numel"):      # gather on the device: only the sample crosses the link
+                import torch
+                t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            else:
+                t = t.reshape(-1)[idx]
+        v = (t.cpu().numpy() if hasattr(t, "numel") else np.asarray(t)).reshape(-1).view(np.uint64)
+        rows = np.stack([(v & np.uint64(0xFFFFFFFF)).astype(np.float64), (v >> np.uint64(32)).astype(np.float64)], axis=1)
+        np.save(os.path.join(dirname, name + ".npy"), rows)
+        if idx is not None:
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
 
 
 KERNEL_SOURCES = ("ronkathon_amd/csrc/ntt_tile.h", "ronkathon_amd/csrc/gl64.h", "ronkathon_amd/csrc/plan.h",
@@ -240,8 +273,14 @@ def main():
     ap.add_argument("--twf", type=int, default=-1, help="largest full inter-pass twiddle matrix, log2 entries (-1 = library default)")
     ap.add_argument("--ranks", type=int, default=0, help="sharded: logical ranks (default: one per visible GPU)")
     ap.add_argument("--chunks", type=int, default=0, help="sharded: column chunks of the exchange (0 = default, up to 4)")
-    ap.add_argument("--samples", type=int, default=5, help="timed regions of --steps steps each (median reported)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle check of the timed plans")
+    ap.add_argument("--samples", type=int, default=None,
+                    help="timed regions of --steps steps each (median reported; default 1, with --full 5)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the oracle check of the timed plans")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: oracle check, CPU baseline, warm / one-at-a-time regimes, per-pass "
+                         "times, counter-based roofline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", dest="dump_outputs",
+                    help="write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     ap.add_argument("--mode", default="auto", choices=["auto", "many", "batch", "streams"],
                     help="ntt22: how the K transforms of a region reach the library -- many: ONE plan handle (in_flight = 2), "
                          "ronk_ntt_forward_many_dev with --group arrays per call; batch: ONE plan of batch --group, K/group calls; "
@@ -263,6 +302,10 @@ def main():
     args = ap.parse_args()
     if args.gpus <= 0:      # `torchrun --nproc-per-node N bench.py` without --gpus: the launcher's world is the job
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.samples is None:
+        args.samples = 5 if args.full else 1
+    if args.dump_outputs and args.workload in ("fourstep", "sharded", "e2e22"):
+        sys.exit("bench.py: --dump-outputs is not supported for --workload %s" % args.workload)
 
     # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, the contract's
     # torch.distributed.run command line), then fall through as rank RANK of WORLD_SIZE.  Under a launcher the two must agree.
@@ -361,7 +404,7 @@ def main():
         def one():
             L.check(L.lib.ronk_msm_bn254_dev(dp.data_ptr(), ds.data_ptr(), nn, L.ptr(out), 0))
         verified = None
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             one()
             a = np.tile(np.arange(1, m + 1, dtype=object), nn // m)
             ks = sw[:, 0].astype(object) + (sw[:, 1].astype(object) << 64) + (sw[:, 2].astype(object) << 128) + (sw[:, 3].astype(object) << 192)
@@ -381,8 +424,10 @@ def main():
             torch.cuda.synchronize()
             dts.append((time.perf_counter() - t0) / steps)
         dt = float(np.median(dts))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"msm_point": out})
         cpu = None
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             # the oracle's fold (affine add, Python integers) on a bounded sample
             k = 256
             kk = [int(sw[i, 0]) | (int(sw[i, 1]) << 64) | (int(sw[i, 2]) << 128) | (int(sw[i, 3]) << 192) for i in range(k)]
@@ -437,7 +482,7 @@ def main():
             for _ in range(calls):
                 L.check(L.lib.ronk_ntt_forward(bplan.h, L.ptr(xh), L.ptr(yh), None))
         verified = None
-        if not args.no_verify:
+        if args.full and not args.no_verify:
             import oracle as orc
             single(1); batched(1)
             want = orc.fft(P, G, x1)
@@ -507,9 +552,11 @@ def main():
         # where the time of ONE transform goes when its stages do not overlap (ronk_sharded_time_stages): phase 1, the whole
         # exchange, phase 2, and the achieved rate per directed link -- so that a first run on a real node can be read without a
         # second lease (a link rate far below xGMI's, or staged pairs above, says the exchange is not travelling peer-to-peer)
-        stage_runs = [sp.time_stages(ip, op) for _ in range(3)]
-        stages = min(stage_runs, key=lambda d_: d_["phase1_ms"] + d_["exchange_ms"] + d_["phase2_ms"])
-        stages["overlap_gain_ms"] = stages["phase1_ms"] + stages["exchange_ms"] + stages["phase2_ms"] - dt / args.steps * 1e3
+        stages = None
+        if args.full:
+            stage_runs = [sp.time_stages(ip, op) for _ in range(3)]
+            stages = min(stage_runs, key=lambda d_: d_["phase1_ms"] + d_["exchange_ms"] + d_["phase2_ms"])
+            stages["overlap_gain_ms"] = stages["phase1_ms"] + stages["exchange_ms"] + stages["phase2_ms"] - dt / args.steps * 1e3
         print(json.dumps({"metric": "sharded four-step forward NTTs/s (in-library, single process), degree 2^%d" % lg,
                           "value": args.steps / dt, "unit": "NTT/s", "n_gpus": ndev, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": dt / args.steps * 1e3, "min_ms_per_step": min(dts) / args.steps * 1e3,
@@ -571,9 +618,9 @@ def main():
     else:
         plans = [L.Plan(P, G, log2n, batch, local_rank, tile_log2_columns=tile_lc, twiddle_matrix_log2_max=args.twf,
                         in_flight=1 if wl == "ntt22" else -1) for _ in range(S)]
-    # latency plan: one transform at a time on one stream, library defaults
+    # latency plan (--full): one transform at a time on one stream, library defaults
     lat_plan = (L.Plan(P, G, log2n, batch, local_rank, twiddle_matrix_log2_max=args.twf, in_flight=1)
-                if (wl == "ntt22" and (tile_lc >= 0 or mode != "streams")) else plans[0])
+                if (args.full and wl == "ntt22" and (tile_lc >= 0 or mode != "streams")) else plans[0])
     if wl in ("ntt22", "batch16", "roundtrip16"):
         assert lat_plan.path() == (2 if mont else 1), "the timed plan does not run the tile kernels (ronk_plan_path)"
     x, y, plan, stream = xs[0], ys[0], plans[0], main_stream.cuda_stream
@@ -723,7 +770,7 @@ def main():
             checked.append("first 2^16 elements == oracle")
         return checked
 
-    verified_what = verify() if not args.no_verify else None
+    verified_what = verify() if (args.full and not args.no_verify) else None
 
     # ---- timing: W untimed warmup steps, a spin-up of untimed steps until the device has been busy >= 50 ms (clocks),
     # then SAMPLES regions of exactly K steps each, every one bracketed by barrier + synchronize on both sides and
@@ -736,12 +783,12 @@ def main():
 
     SAMPLES = max(1, args.samples)
 
-    def timed_regions():
+    def timed_regions(count=SAMPLES):
         """SAMPLES regions of exactly K steps, each bracketed by barrier + synchronize on both sides: wall seconds per region
         (max over ranks) and, for the SAME regions, the device time between two HIP events recorded on the launch stream
         right after the opening and right before the closing synchronisation (milliseconds, this rank)"""
         out_, dev_ = [], []
-        for _ in range(SAMPLES):
+        for _ in range(count):
             e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             sync_all()
             t0_ = time.perf_counter()
@@ -776,6 +823,9 @@ def main():
     while time.perf_counter() - t_spin < 0.05:
         run(max(1, args.steps))
         torch.cuda.synchronize()
+    # one untimed region of the same shape first: the first region of a process takes a fixed ~30 us longer than the ones
+    # after it (MI355X, 2^22: 0.0437-0.0440 against ~0.042 ms per step at 20 steps, no difference at 400)
+    timed_regions(1)
     dts, dts_dev = timed_regions()                        # the protocol of `value`: throughput mode, R_cold buffers
     dt = float(np.median(dts))
     dt_min = float(min(dts))
@@ -783,147 +833,172 @@ def main():
     # same regime on the device clock (events); with several CALLER streams an event on one of them does not bracket the
     # others' work: the wall time of the region stands in
     thr_dev_ms = float(np.median(dts_dev)) if S == 1 else dt * 1e3
-    warm = None
-    # warm = the same buffers every step (Infinity-Cache resident inputs): one pair per transform in flight (the two lanes of
-    # the many mode must not write ONE output buffer at the same time)
-    R_warm = 2 if (wl == "ntt22" and mode == "many") else 1
-    if R_cold > R_warm:
-        rot["R"] = R_warm
-        run(max(10, args.steps))
-        dts_w, _ = timed_regions()
-        warm = {"value": world * args.steps * batch / float(np.median(dts_w)), "ms_per_step": float(np.median(dts_w)) / args.steps * 1e3,
-                "rotate": R_warm, "note": "the round-1/2 protocol: every step transforms the same buffers (inputs stay in the "
-                                          "256 MiB Infinity Cache); `value` is the HBM-cold protocol (rotate = %d)" % R_cold}
-    # Latency regime: the same K steps one at a time on ONE stream with the default plan (kernel durations add up)
-    S_saved, S = S, 1
-    rot["R"], rot["lat"] = R_cold, wl == "ntt22"
-    if not rot["lat"]:
-        plan0, plans[0] = plans[0], lat_plan
-    run(max(10, args.steps))
-    dev_ms_samples = device_regions()
-    dev_ms = float(np.median(dev_ms_samples))
-    lat_warm_ms = None
-    if R_cold > 1:
-        rot["R"] = 1
-        run(max(10, args.steps))
-        lat_warm_ms = float(np.median(device_regions()))
-    rot["R"], rot["lat"] = R_cold, False
-    S = S_saved
-    if wl != "ntt22":
-        plans[0] = plan0
-
-    # per-kernel device time (hipEvents on the launch stream) for the roofline of the dominant kernel
-    pass_ms = None
-    if wl in ("ntt22", "batch16"):
-        pass_ms = lat_plan.time_passes(x.data_ptr(), y.data_ptr(), inverse=False, iters=50, stream=stream)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed (nothing has run since): its output buffer, by the cycling of run()
+        if wl in ("ntt22", "batch16"):
+            last = args.steps - 1
+            if mode == "many":
+                k_, r_ = 0, last % R_cold
+            elif mode == "batch":
+                k_, r_ = 0, (args.steps // group - 1) % R_cold
+            else:
+                k_, r_ = last % S, (last // S) % R_cold
+            outs = {"ntt_forward": ypool[k_][r_]}
+        elif wl == "mul22":
+            outs = {"product": out}
+        elif wl == "open22":
+            outs = {"quotient": y, "remainder": scal}
+        elif wl == "eval22":
+            outs = {"value": scal}
+        else:                                              # vecmul24 / vecadd24 / rs16 / roundtrip16 (= its input again)
+            outs = {"output": y}
+        dump_outputs(args.dump_outputs, outs)
     alg_bytes_step = wl_bytes_per_n * (batch / wl_batch) * n
-    step_s = (dev_ms / 1e3) / args.steps                             # device time per step on the launch stream
-    achieved = alg_bytes_step / step_s / 1e9              # latency regime
+    achieved_wall = alg_bytes_step / (dt / args.steps) / 1e9
     thr_step_s = (thr_dev_ms / 1e3) / args.steps                     # throughput regime (device clock, same regime as value)
     achieved_thr = alg_bytes_step / thr_step_s / 1e9
-    # HBM bytes per launch from the PMC passes of the same command under rocprofv3 (tools/profile.sh ->
-    # tools/rocprof_summary.py; FETCH_SIZE x2 gfx950 correction, calibrated on this kernel's known byte count).
-    # bench.py cannot read PMCs itself: it reports the committed measurement of the dominant kernel IF that file was
-    # taken on the current kernel sources (hash stored in the file), else null.
-    # Which file: the counters of the kernels `value` RAN.  The headline's regime is two lanes on the 4-column kernels
-    # (ntt_tile_kernel<11, false, 2, *>): profiles/latest_pmc_ntt22.json is taken from exactly this command line
-    # (tools/profile_all.sh, "many"); the one-transform-at-a-time kernels (8-column tiles) have their own file, reported as
-    # roofline.latency_regime.  A Montgomery prime runs other kernels again: latest_pmc_ntt22_mont.json.
-    traffic, traffic_note, valu = None, None, None
-    pmc_key = wl + ("_mont" if mont else "") + ("_1stream" if (wl == "ntt22" and mode == "streams" and S == 1) else "")
-    pmc, why = load_if_current("profiles/latest_pmc_%s.json" % pmc_key, wl)
-    if pmc and log2n == wl_log2n and batch == wl_batch:
-        # every kernel of the step that moved data (the passes of a transform; the two scan kernels of a division): the
-        # step's traffic and VALU count are SUMS over them, each counted once per step
-        # (the library's kernels only: under the profiler the same process also runs torch's roll / fill kernels while it sets
-        # its buffers up, once, not per step)
-        kerns = [kname for kname, c in pmc.get("counters", {}).items() if "_hbm_bytes_per_launch" in c and "ronk::" in kname]
-        if wl in ("ntt22", "batch16"):
-            # the profiled command also runs the OTHER regime's plan once per sample (the one-at-a-time measurement inside this
-            # script: 8-column kernels next to the two-lane regime's 4-column ones): a step is the `num_passes` kernels that were
-            # launched most often (the trace's call counts)
-            calls = {k_["name"]: k_["calls"] for k_ in pmc.get("kernels", [])}
-            kerns.sort(key=lambda kname: -calls.get(kname, 0))
-            kerns = kerns[:plan.num_passes()]
-        kerns.sort(key=lambda kname: -pmc["counters"][kname].get("_avg_us", 0))
-        if kerns:
-            cs = [pmc["counters"][kname] for kname in kerns]
-            traffic = sum(c["_hbm_bytes_per_launch"]["total"] for c in cs)
-            traffic_note = ("fabric-side bytes per STEP = sum over the %d kernel(s) of a step (%s) of FETCH_SIZE x2 (gfx950 "
-                            "correction) + WRITE_SIZE per launch (rocprofv3 PMC, profiles/%s); these counters include "
-                            "Infinity-Cache hits (MI355X_MICROARCH.md), so this is traffic at the L2's memory side, an upper "
-                            "bound on HBM bytes" % (len(kerns), "; ".join("%s: %.0f" % (k_[:60], c["_hbm_bytes_per_launch"]["total"])
-                                                                         for k_, c in zip(kerns, cs)),
-                                                  pmc.get("source", "latest_pmc_%s.json" % pmc_key)))
-            if wl == "ntt22":
-                traffic_note += ("; algorithmic bytes per step = %d (16*n); a two-pass plan moves 2x that by construction, "
-                                 "anything above is re-reads / split lines" % (16 * n))
-            if all("SQ_INSTS_VALU" in c for c in cs):
-                valu = {"insts_per_coeff": sum(c["SQ_INSTS_VALU"]["avg"] for c in cs) * 64.0 / (n * batch),
-                        "source": "sum over the step's %d kernel(s) of SQ_INSTS_VALU x 64 lanes / coefficients (PMC, same file)" % len(kerns)}
-    else:
-        traffic_note = "no current PMC file for this workload/kernel (%s): re-run tools/profile.sh" % why
-    # Secondary ceiling: 64-bit modular arithmetic is VALU-issue bound.  Static census of the executed
-    # path (tools/census.py: instructions and issue slots per coefficient, weights from tools/instr_rate.hip).
-    if wl == "ntt22" and not mont:
-        cen, why_c = load_if_current("profiles/latest_census.json")
-        if cen:
-            valu = valu or {}
-            issue_us = cen["slots_per_coeff"] * n / VALU_PEAK_LANE_OPS * 1e6
-            valu.update({"static_insts_per_coeff": cen["valu_per_coeff"], "issue_slots_per_coeff": cen["slots_per_coeff"],
-                         "issue_bound_us": issue_us, "frac_of_valu_peak": issue_us / (step_s * 1e6),
-                         "valu_peak_lane_ops_per_s": VALU_PEAK_LANE_OPS,
-                         "note": "issue_bound_us = issue slots per coefficient x n / measured full-rate VALU throughput "
-                                 "(profiles/r01_instr_rate_gfx950.txt); frac_of_valu_peak = issue_bound_us / device time per "
-                                 "transform: how close the kernel is to its own arithmetic ceiling"})
-        elif valu is None:
-            valu = {"note": "census " + why_c}
-    # `achieved` / `frac` follow `value`: the throughput regime, R_cold buffers, device clock over the timed region.  The
-    # latency regime (one transform at a time: kernel durations add up) and the warm variants are reported beside it.
-    # `achieved` / `frac` are computed from the SAME clock as `ms_per_step` (the wall time of the median region, max over
-    # ranks): frac == algorithmic_bytes_per_step / (ms_per_step / 1e3) / 8e12, recomputable from the line itself.  The HIP-event
-    # figure over the same regions (device clock on the launch stream) is reported beside it as frac_device.
-    achieved_wall = alg_bytes_step / (dt / args.steps) / 1e9
-    lat_pmc = None
-    if wl == "ntt22" and not mont and pmc_key == "ntt22":
-        lp, _ = load_if_current("profiles/latest_pmc_ntt22_1stream.json", wl)
-        if lp:
-            lk = [c for kname, c in lp.get("counters", {}).items() if "_hbm_bytes_per_launch" in c and "ronk::" in kname]
-            if lk:
-                lat_pmc = {"traffic": sum(c["_hbm_bytes_per_launch"]["total"] for c in lk),
-                           "valu_insts_per_coeff": (sum(c["SQ_INSTS_VALU"]["avg"] for c in lk) * 64.0 / n
-                                                    if all("SQ_INSTS_VALU" in c for c in lk) else None),
-                           "source": lp.get("source"),
-                           "note": "counters of the kernels frac_latency times (one transform at a time, default plan: 8-column tiles)"}
+    # `achieved` / `frac`: the regime of `value` on the clock of `ms_per_step`; frac_device: HIP events over the same regions
     roofline = {"bound": "hbm", "achieved": achieved_wall, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved_wall / HBM_PEAK_GBS, "frac_device": achieved_thr / HBM_PEAK_GBS,
-                "frac_throughput": achieved_thr / HBM_PEAK_GBS,
-                "frac_latency": achieved / HBM_PEAK_GBS, "latency_regime": lat_pmc,
-                "frac_throughput_warm": (alg_bytes_step * warm["value"] / world / batch / 1e9 / HBM_PEAK_GBS) if warm else None,
-                "frac_latency_warm": (alg_bytes_step / (lat_warm_ms / 1e3 / args.steps) / 1e9 / HBM_PEAK_GBS) if lat_warm_ms else None,
-                "rotate": R_cold,
-                "traffic": traffic,
-                "traffic_note": traffic_note,
-                "kernel": wl_kernel or (
-                    "ntt_tile_wl_col_kernel + ntt_tile_wl_row_kernel (2^11-row x 4-column passes, csrc/ntt_tile_wl.h), 2 launches per NTT"
-                    if (wl == "ntt22" and log2n == 22 and mode in ("many", "streams") and os.environ.get("RONK_WL", "1") != "0"
-                        and (mode == "many" or args.tile_logc == 2))
-                    else "ntt_tile_kernel<%d> x %d launches per NTT" % ((log2n + 1) // 2 if log2n > 12 else log2n, plan.num_passes())),
-                "algorithmic_bytes_per_step": alg_bytes_step, "device_us_per_step": step_s * 1e6,
-                "device_us_per_step_min": min(dev_ms_samples) * 1e3 / args.steps,
-                "note": "achieved / frac: the regime of `value` (%s) on the clock of ms_per_step (wall, median region); frac_device / "
-                        "frac_throughput: HIP events on the launch stream over the same "
-                        "timed regions; inputs and outputs cycling over %d buffer pairs (%d MiB touched between two uses of a "
-                        "buffer); frac_latency: one transform at a time on ONE stream, default plan (kernel durations add up), "
-                        "same rotation; *_warm: the same buffers every step (inputs stay in the 256 MiB Infinity Cache); median of "
-                        "%d regions of %d steps" % (
-                            {"many": "ONE plan handle, in_flight = 2, ronk_ntt_forward_many_dev, %d arrays per call" % group,
-                             "batch": "ONE plan handle of batch %d" % group,
-                             "streams": "%d caller streams, one plan each" % S}[mode] if wl == "ntt22" else "one stream",
-                            R_cold, R_cold * 2 * pb * n * 8 >> 20, SAMPLES, args.steps),
-                "throughput_GBs": alg_bytes_step * args.steps / dt / 1e9,
-                "pass_us": [m * 1e3 for m in pass_ms] if pass_ms else None,
-                "valu": valu}
+                "frac": achieved_wall / HBM_PEAK_GBS, "frac_device": achieved_thr / HBM_PEAK_GBS, "rotate": R_cold,
+                "algorithmic_bytes_per_step": alg_bytes_step, "throughput_GBs": alg_bytes_step * args.steps / dt / 1e9}
+    warm = None
+    if args.full:
+        # warm = the same buffers every step (Infinity-Cache resident inputs): one pair per transform in flight (the two lanes of
+        # the many mode must not write ONE output buffer at the same time)
+        R_warm = 2 if (wl == "ntt22" and mode == "many") else 1
+        if R_cold > R_warm:
+            rot["R"] = R_warm
+            run(max(10, args.steps))
+            dts_w, _ = timed_regions()
+            warm = {"value": world * args.steps * batch / float(np.median(dts_w)), "ms_per_step": float(np.median(dts_w)) / args.steps * 1e3,
+                    "rotate": R_warm, "note": "the round-1/2 protocol: every step transforms the same buffers (inputs stay in the "
+                                              "256 MiB Infinity Cache); `value` is the HBM-cold protocol (rotate = %d)" % R_cold}
+        # Latency regime: the same K steps one at a time on ONE stream with the default plan (kernel durations add up)
+        S_saved, S = S, 1
+        rot["R"], rot["lat"] = R_cold, wl == "ntt22"
+        if not rot["lat"]:
+            plan0, plans[0] = plans[0], lat_plan
+        run(max(10, args.steps))
+        dev_ms_samples = device_regions()
+        dev_ms = float(np.median(dev_ms_samples))
+        lat_warm_ms = None
+        if R_cold > 1:
+            rot["R"] = 1
+            run(max(10, args.steps))
+            lat_warm_ms = float(np.median(device_regions()))
+        rot["R"], rot["lat"] = R_cold, False
+        S = S_saved
+        if wl != "ntt22":
+            plans[0] = plan0
+
+        # per-kernel device time (hipEvents on the launch stream) for the roofline of the dominant kernel
+        pass_ms = None
+        if wl in ("ntt22", "batch16"):
+            pass_ms = lat_plan.time_passes(x.data_ptr(), y.data_ptr(), inverse=False, iters=50, stream=stream)
+        step_s = (dev_ms / 1e3) / args.steps                             # device time per step on the launch stream
+        achieved = alg_bytes_step / step_s / 1e9              # latency regime
+        # HBM bytes per launch from the PMC passes of the same command under rocprofv3 (tools/profile.sh ->
+        # tools/rocprof_summary.py; FETCH_SIZE x2 gfx950 correction, calibrated on this kernel's known byte count).
+        # bench.py cannot read PMCs itself: it reports the committed measurement of the dominant kernel IF that file was
+        # taken on the current kernel sources (hash stored in the file), else null.
+        # Which file: the counters of the kernels `value` RAN.  The headline's regime is two lanes on the 4-column kernels
+        # (ntt_tile_kernel<11, false, 2, *>): profiles/latest_pmc_ntt22.json is taken from exactly this command line
+        # (tools/profile_all.sh, "many"); the one-transform-at-a-time kernels (8-column tiles) have their own file, reported as
+        # roofline.latency_regime.  A Montgomery prime runs other kernels again: latest_pmc_ntt22_mont.json.
+        traffic, traffic_note, valu = None, None, None
+        pmc_key = wl + ("_mont" if mont else "") + ("_1stream" if (wl == "ntt22" and mode == "streams" and S == 1) else "")
+        pmc, why = load_if_current("profiles/latest_pmc_%s.json" % pmc_key, wl)
+        if pmc and log2n == wl_log2n and batch == wl_batch:
+            # every kernel of the step that moved data (the passes of a transform; the two scan kernels of a division): the
+            # step's traffic and VALU count are SUMS over them, each counted once per step
+            # (the library's kernels only: under the profiler the same process also runs torch's roll / fill kernels while it sets
+            # its buffers up, once, not per step)
+            kerns = [kname for kname, c in pmc.get("counters", {}).items() if "_hbm_bytes_per_launch" in c and "ronk::" in kname]
+            if wl in ("ntt22", "batch16"):
+                # the profiled command also runs the OTHER regime's plan once per sample (the one-at-a-time measurement inside this
+                # script: 8-column kernels next to the two-lane regime's 4-column ones): a step is the `num_passes` kernels that were
+                # launched most often (the trace's call counts)
+                calls = {k_["name"]: k_["calls"] for k_ in pmc.get("kernels", [])}
+                kerns.sort(key=lambda kname: -calls.get(kname, 0))
+                kerns = kerns[:plan.num_passes()]
+            kerns.sort(key=lambda kname: -pmc["counters"][kname].get("_avg_us", 0))
+            if kerns:
+                cs = [pmc["counters"][kname] for kname in kerns]
+                traffic = sum(c["_hbm_bytes_per_launch"]["total"] for c in cs)
+                traffic_note = ("fabric-side bytes per STEP = sum over the %d kernel(s) of a step (%s) of FETCH_SIZE x2 (gfx950 "
+                                "correction) + WRITE_SIZE per launch (rocprofv3 PMC, profiles/%s); these counters include "
+                                "Infinity-Cache hits (MI355X_MICROARCH.md), so this is traffic at the L2's memory side, an upper "
+                                "bound on HBM bytes" % (len(kerns), "; ".join("%s: %.0f" % (k_[:60], c["_hbm_bytes_per_launch"]["total"])
+                                                                             for k_, c in zip(kerns, cs)),
+                                                      pmc.get("source", "latest_pmc_%s.json" % pmc_key)))
+                if wl == "ntt22":
+                    traffic_note += ("; algorithmic bytes per step = %d (16*n); a two-pass plan moves 2x that by construction, "
+                                     "anything above is re-reads / split lines" % (16 * n))
+                if all("SQ_INSTS_VALU" in c for c in cs):
+                    valu = {"insts_per_coeff": sum(c["SQ_INSTS_VALU"]["avg"] for c in cs) * 64.0 / (n * batch),
+                            "source": "sum over the step's %d kernel(s) of SQ_INSTS_VALU x 64 lanes / coefficients (PMC, same file)" % len(kerns)}
+        else:
+            traffic_note = "no current PMC file for this workload/kernel (%s): re-run tools/profile.sh" % why
+        # Secondary ceiling: 64-bit modular arithmetic is VALU-issue bound.  Static census of the executed
+        # path (tools/census.py: instructions and issue slots per coefficient, weights from tools/instr_rate.hip).
+        if wl == "ntt22" and not mont:
+            cen, why_c = load_if_current("profiles/latest_census.json")
+            if cen:
+                valu = valu or {}
+                issue_us = cen["slots_per_coeff"] * n / VALU_PEAK_LANE_OPS * 1e6
+                valu.update({"static_insts_per_coeff": cen["valu_per_coeff"], "issue_slots_per_coeff": cen["slots_per_coeff"],
+                             "issue_bound_us": issue_us, "frac_of_valu_peak": issue_us / (step_s * 1e6),
+                             "valu_peak_lane_ops_per_s": VALU_PEAK_LANE_OPS,
+                             "note": "issue_bound_us = issue slots per coefficient x n / measured full-rate VALU throughput "
+                                     "(profiles/r01_instr_rate_gfx950.txt); frac_of_valu_peak = issue_bound_us / device time per "
+                                     "transform: how close the kernel is to its own arithmetic ceiling"})
+            elif valu is None:
+                valu = {"note": "census " + why_c}
+        # `achieved` / `frac` follow `value`: the throughput regime, R_cold buffers, device clock over the timed region.  The
+        # latency regime (one transform at a time: kernel durations add up) and the warm variants are reported beside it.
+        # `achieved` / `frac` are computed from the SAME clock as `ms_per_step` (the wall time of the median region, max over
+        # ranks): frac == algorithmic_bytes_per_step / (ms_per_step / 1e3) / 8e12, recomputable from the line itself.  The HIP-event
+        # figure over the same regions (device clock on the launch stream) is reported beside it as frac_device.
+        lat_pmc = None
+        if wl == "ntt22" and not mont and pmc_key == "ntt22":
+            lp, _ = load_if_current("profiles/latest_pmc_ntt22_1stream.json", wl)
+            if lp:
+                lk = [c for kname, c in lp.get("counters", {}).items() if "_hbm_bytes_per_launch" in c and "ronk::" in kname]
+                if lk:
+                    lat_pmc = {"traffic": sum(c["_hbm_bytes_per_launch"]["total"] for c in lk),
+                               "valu_insts_per_coeff": (sum(c["SQ_INSTS_VALU"]["avg"] for c in lk) * 64.0 / n
+                                                        if all("SQ_INSTS_VALU" in c for c in lk) else None),
+                               "source": lp.get("source"),
+                               "note": "counters of the kernels frac_latency times (one transform at a time, default plan: 8-column tiles)"}
+        roofline = {"bound": "hbm", "achieved": achieved_wall, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved_wall / HBM_PEAK_GBS, "frac_device": achieved_thr / HBM_PEAK_GBS,
+                    "frac_throughput": achieved_thr / HBM_PEAK_GBS,
+                    "frac_latency": achieved / HBM_PEAK_GBS, "latency_regime": lat_pmc,
+                    "frac_throughput_warm": (alg_bytes_step * warm["value"] / world / batch / 1e9 / HBM_PEAK_GBS) if warm else None,
+                    "frac_latency_warm": (alg_bytes_step / (lat_warm_ms / 1e3 / args.steps) / 1e9 / HBM_PEAK_GBS) if lat_warm_ms else None,
+                    "rotate": R_cold,
+                    "traffic": traffic,
+                    "traffic_note": traffic_note,
+                    "kernel": wl_kernel or (
+                        "ntt_tile_wl_col_kernel + ntt_tile_wl_row_kernel (2^11-row x 4-column passes, csrc/ntt_tile_wl.h), 2 launches per NTT"
+                        if (wl == "ntt22" and log2n == 22 and mode in ("many", "streams") and os.environ.get("RONK_WL", "1") != "0"
+                            and (mode == "many" or args.tile_logc == 2))
+                        else "ntt_tile_kernel<%d> x %d launches per NTT" % ((log2n + 1) // 2 if log2n > 12 else log2n, plan.num_passes())),
+                    "algorithmic_bytes_per_step": alg_bytes_step, "device_us_per_step": step_s * 1e6,
+                    "device_us_per_step_min": min(dev_ms_samples) * 1e3 / args.steps,
+                    "note": "achieved / frac: the regime of `value` (%s) on the clock of ms_per_step (wall, median region); frac_device / "
+                            "frac_throughput: HIP events on the launch stream over the same "
+                            "timed regions; inputs and outputs cycling over %d buffer pairs (%d MiB touched between two uses of a "
+                            "buffer); frac_latency: one transform at a time on ONE stream, default plan (kernel durations add up), "
+                            "same rotation; *_warm: the same buffers every step (inputs stay in the 256 MiB Infinity Cache); median of "
+                            "%d regions of %d steps" % (
+                                {"many": "ONE plan handle, in_flight = 2, ronk_ntt_forward_many_dev, %d arrays per call" % group,
+                                 "batch": "ONE plan handle of batch %d" % group,
+                                 "streams": "%d caller streams, one plan each" % S}[mode] if wl == "ntt22" else "one stream",
+                                R_cold, R_cold * 2 * pb * n * 8 >> 20, SAMPLES, args.steps),
+                    "throughput_GBs": alg_bytes_step * args.steps / dt / 1e9,
+                    "pass_us": [m * 1e3 for m in pass_ms] if pass_ms else None,
+                    "valu": valu}
 
     # how many ranks really took part (an all-reduce of 1 over the job): the driver can check it against --gpus
     ranks_seen = 1
@@ -939,9 +1014,9 @@ def main():
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": dt / args.steps * 1e3, "min_ms_per_step": dt_min / args.steps * 1e3,
                "samples_ms_per_step": [t / args.steps * 1e3 for t in dts],
-               "timing": "median of %d regions of exactly %d steps after %d warmup steps + >= 50 ms spin-up; each region "
-                         "bracketed by barrier + torch.cuda.synchronize, max over ranks" % (SAMPLES, args.steps, args.warmup),
-               "verified": bool(verified_what), "verified_how": verified_what,
+               "timing": "median of %d regions of exactly %d steps after %d warmup steps, a >= 50 ms spin-up and one untimed "
+                         "region; each region bracketed by barrier + torch.cuda.synchronize, max over ranks" % (SAMPLES, args.steps, args.warmup),
+               "verified": bool(verified_what) if args.full else None, "verified_how": verified_what,
                "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "u64", "data": "synthetic",
                "config": {"workload": "forward NTT, n = 2^%d, batch %d, %s, natural order in/out, device resident"
@@ -954,14 +1029,15 @@ def main():
                               "in_flight": plans[0].in_flight() if hasattr(L.lib, "ronk_plan_in_flight") else None})
         res["ranks_seen"] = ranks_seen
         assert ranks_seen == args.gpus, "ranks_seen %d != --gpus %d" % (ranks_seen, args.gpus)
-        if not args.no_cpu and world == 1 and wl == "ntt22":       # reported at N = 1 only (bench contract)
-            res["cpu_baseline"] = cpu_baseline(log2n, p=P, g=G)
-        if not args.no_cpu and world == 1 and wl in ("batch16", "rs16"):
-            res["cpu_baseline"] = cpu_baseline_batched(log2n)
-        if not args.no_cpu and world == 1 and wl == "mul22":
-            res["cpu_baseline"] = cpu_baseline_mul(log2n)
-        if not args.no_cpu and world == 1 and wl == "roundtrip16":
-            res["cpu_baseline"] = cpu_baseline_roundtrip(log2n)
+        if args.full and not args.no_cpu and world == 1:       # reported at N = 1 only (bench contract)
+            if wl == "ntt22":
+                res["cpu_baseline"] = cpu_baseline(log2n, p=P, g=G)
+            if wl in ("batch16", "rs16"):
+                res["cpu_baseline"] = cpu_baseline_batched(log2n)
+            if wl == "mul22":
+                res["cpu_baseline"] = cpu_baseline_mul(log2n)
+            if wl == "roundtrip16":
+                res["cpu_baseline"] = cpu_baseline_roundtrip(log2n)
         print(json.dumps(res), flush=True)
     for p_ in plans + [lat_plan]:
         p_.close()
@@ -969,7 +1045,7 @@ def main():
     # BASELINE config 5 (2^26 over the ranks, one RCCL all-to-all over xGMI per transform).  Result goes to
     # stderr and gpurun_out/; any failure here is reported, not raised.  Opt-in (RONK_BENCH_FOURSTEP=1) so that the
     # scaling run of the default benchmark never depends on a collective that was not asked for.
-    if world > 1 and wl == "ntt22" and os.environ.get("RONK_BENCH_FOURSTEP", "0") == "1":
+    if args.full and world > 1 and wl == "ntt22" and os.environ.get("RONK_BENCH_FOURSTEP", "0") == "1":
         try:
             from ronkathon_amd import dist as rdist
             fs = rdist.bench_fourstep(26, 20, 3)

@@ -1,17 +1,15 @@
 """rust/ronk-goldilocks/in_tree/ronkathon.patch: the edit that makes ronkathon's own `poly.fft()` / `a * b` / `a / b` call
-sites reach the GPU for `Goldilocks` (row N3 of SURVEY.md 8f).  No rustc here, so what can be checked is checked:
-the patch applies cleanly to the reference (`git apply --check` on a scratch copy), it is the one the generator produces
-from the crate's current sources, and the vendored FFI block is the crate's FFI block."""
+sites reach the GPU for `Goldilocks` (row N3 of SURVEY.md 8f).  The suite compiles no Rust, so what can be checked is
+checked, from the repository alone: the patch applies cleanly (`git apply --check`) to the pre-image its own hunks record, it is the one the
+generator produces from the crate's current sources, and the vendored FFI block is the crate's FFI block."""
+import importlib.util
 import os
-import shutil
+import re
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PATCH = os.path.join(ROOT, "rust", "ronk-goldilocks", "in_tree", "ronkathon.patch")
-REF = "/root/reference"
 
 
 def new_file_body(patch, path):
@@ -39,12 +37,38 @@ def test_patch_vendors_the_crate_ffi_verbatim():
     assert "unimplemented!" not in patch
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is only present in the build container")
-def test_patch_applies_to_the_reference_and_is_current(tmp_path):
+def patch_preimages(patch):
+    """the edited files as far as the patch shows them: context and removed lines of every hunk, in order"""
+    out = {}
+    for part in re.split(r"(?m)^(?=diff --git )", patch):
+        if not part or "\nnew file mode" in part:
+            continue
+        path = re.match(r"diff --git a/(\S+)", part).group(1)
+        out[path] = "".join(ln[1:] for ln in part.splitlines(keepends=True)
+                            if ln.startswith((" ", "-")) and not ln.startswith("--- "))
+    return out
+
+
+def load_generator():
+    """tools/make_in_tree_patch.py as a module (its command line is parsed at import: give it an empty one)"""
+    argv, sys.argv = sys.argv, [os.path.join(ROOT, "tools", "make_in_tree_patch.py")]
+    try:
+        spec = importlib.util.spec_from_file_location("make_in_tree_patch", sys.argv[0])
+        gen = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(gen)
+    finally:
+        sys.argv = argv
+    return gen
+
+
+def test_patch_applies_to_its_preimage_and_is_current(tmp_path):
+    patch = open(PATCH).read()
+    pre = patch_preimages(patch)
+    assert sorted(pre) == ["Cargo.toml", "src/algebra/field/mod.rs", "src/polynomial/arithmetic.rs", "src/polynomial/mod.rs"]
     scratch = tmp_path / "ronkathon"
-    scratch.mkdir()
-    shutil.copytree(os.path.join(REF, "src"), scratch / "src")
-    shutil.copy(os.path.join(REF, "Cargo.toml"), scratch / "Cargo.toml")
+    for rel, text in pre.items():
+        (scratch / rel).parent.mkdir(parents=True, exist_ok=True)
+        (scratch / rel).write_text(text)
     subprocess.check_call(["git", "init", "-q", "."], cwd=scratch)
     subprocess.check_call(["git", "apply", "--check", PATCH], cwd=scratch)
     subprocess.check_call(["git", "apply", PATCH], cwd=scratch)
@@ -56,9 +80,17 @@ def test_patch_applies_to_the_reference_and_is_current(tmp_path):
     for f in ("build.rs", "src/polynomial/dispatch.rs", "src/algebra/field/goldilocks/mod.rs", "src/algebra/field/goldilocks/ffi.rs",
               "src/algebra/field/goldilocks/gpu.rs"):
         assert (scratch / f).is_file()
-    # the committed patch is what the generator makes from the crate's sources today (written to a scratch file: the tracked
-    # patch is only read)
-    fresh = tmp_path / "fresh.patch"
-    subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "make_in_tree_patch.py"), REF, "--output=%s" % fresh],
-                          stdout=subprocess.DEVNULL)
-    assert fresh.read_text() == open(PATCH).read(), "rust sources changed: re-run tools/make_in_tree_patch.py and commit the patch"
+    # the committed patch is what the generator makes today: its edits turn each pre-image into the patched file (the
+    # anchors of polynomial/mod.rs reach past the hunks' context, so that file is checked by the names above), and the new
+    # files are the generator's output from the crate's sources, byte for byte
+    gen = load_generator()
+    for rel, edit in (("Cargo.toml", gen.edit_cargo), ("src/algebra/field/mod.rs", gen.edit_field_mod),
+                      ("src/polynomial/arithmetic.rs", gen.edit_polynomial_arithmetic)):
+        assert edit(pre[rel]) == (scratch / rel).read_text(), rel
+    crate = os.path.join(ROOT, "rust", "ronk-goldilocks", "src")
+    new = "".join([gen.udiff(None, gen.BUILD_RS, "build.rs"),
+                   gen.udiff(None, gen.vendor_ffi(gen.read(os.path.join(crate, "ffi.rs"))), "src/algebra/field/goldilocks/ffi.rs"),
+                   gen.udiff(None, gen.vendor_gpu(gen.read(os.path.join(crate, "polynomial.rs"))), "src/algebra/field/goldilocks/gpu.rs"),
+                   gen.udiff(None, gen.vendor_field(gen.read(os.path.join(crate, "field.rs"))), "src/algebra/field/goldilocks/mod.rs"),
+                   gen.udiff(None, gen.DISPATCH_RS, "src/polynomial/dispatch.rs")])
+    assert patch[patch.index("diff --git a/build.rs"):] == new, "rust sources changed: re-run tools/make_in_tree_patch.py and commit the patch"

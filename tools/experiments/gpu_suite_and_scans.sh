@@ -1,6 +1,6 @@
 O=gpurun_out/r02x; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q --timeout 600 2>&1 | tail -3
-for w in open22 eval22; do timeout 120 python bench.py --no-cpu --workload $w --steps 200 --warmup 20 > $O/$w.json 2>> $O/err; done
+for w in open22 eval22; do timeout 120 python bench.py --full --no-cpu --workload $w --steps 200 --warmup 20 > $O/$w.json 2>> $O/err; done
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r02x/*.json')):

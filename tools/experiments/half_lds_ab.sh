@@ -2,7 +2,7 @@
 O=gpurun_out/r02s; mkdir -p $O
 run() { # name, env, args...
   local name=$1; local envs=$2; shift 2
-  env $envs timeout 120 python bench.py --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err
+  env $envs timeout 120 python bench.py --full --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err
 }
 for h in 0 1; do
   run b16_h$h RONK_HALF_LDS=$h --workload batch16 --steps 50 --warmup 10

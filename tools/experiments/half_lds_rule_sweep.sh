@@ -1,6 +1,6 @@
 O=gpurun_out/r02v; mkdir -p $O
 run() { local name=$1; local envs=$2; shift 2
-  env $envs timeout 120 python bench.py --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
+  env $envs timeout 120 python bench.py --full --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
 for h in 0 1 d; do
   E=RONK_HALF_LDS=$h; [ $h = d ] && E=RONK_DUMMY=1
   run b16_h$h $E --workload batch16 --steps 50 --warmup 10

@@ -1,6 +1,6 @@
 O=gpurun_out/r02y; mkdir -p $O
-for lg in 16 18 20; do timeout 300 python bench.py --workload msm20 --log2n $lg --no-cpu --steps 5 --samples 3 > $O/msm$lg.json 2>> $O/err; done
-for c in 12 13 14 16; do RONK_MSM_C=$c timeout 300 python bench.py --workload msm20 --log2n 20 --no-cpu --no-verify --steps 5 --samples 3 > $O/msm20_c$c.json 2>> $O/err; done
+for lg in 16 18 20; do timeout 300 python bench.py --full --workload msm20 --log2n $lg --no-cpu --steps 5 --samples 3 > $O/msm$lg.json 2>> $O/err; done
+for c in 12 13 14 16; do RONK_MSM_C=$c timeout 300 python bench.py --full --workload msm20 --log2n 20 --no-cpu --no-verify --steps 5 --samples 3 > $O/msm20_c$c.json 2>> $O/err; done
 python - <<'PY'
 import json,glob
 for f in sorted(glob.glob('gpurun_out/r02y/*.json')):

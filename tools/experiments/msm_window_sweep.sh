@@ -1,6 +1,6 @@
 O=gpurun_out/r02ag; mkdir -p $O
 for lg in 14 16 18 20 22; do for d in 9 8 7 6 5 4; do c=$((lg-d)); [ $c -lt 6 ] && continue; [ $c -gt 16 ] && continue
-  RONK_MSM_C=$c timeout 300 python bench.py --workload msm20 --log2n $lg --no-cpu --no-verify --steps 5 --samples 3 > $O/msm${lg}_c$c.json 2>> $O/err; done; done
+  RONK_MSM_C=$c timeout 300 python bench.py --full --workload msm20 --log2n $lg --no-cpu --no-verify --steps 5 --samples 3 > $O/msm${lg}_c$c.json 2>> $O/err; done; done
 python - <<'PY'
 import json,glob,re
 rows={}

@@ -1,7 +1,7 @@
 O=gpurun_out/r02w; mkdir -p $O
 timeout 600 python -m pytest tests -m gpu -x -q --timeout 600 -k "scan or horner or divrem or linear" 2>&1 | tail -5
 run() { local name=$1; local envs=$2; shift 2
-  env $envs timeout 120 python bench.py --no-cpu "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
+  env $envs timeout 120 python bench.py --full --no-cpu "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
 for v in new old; do
   E=RONK_DUMMY=1; [ $v = old ] && E=RONK_NO_ONEPASS_SCANS=1
   run open22_$v $E --workload open22 --steps 200 --warmup 20

@@ -1,6 +1,6 @@
 O=gpurun_out/r02ad; mkdir -p $O
 run() { local name=$1; local envs=$2; shift 2
-  env $envs timeout 120 python bench.py --no-cpu "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
+  env $envs timeout 120 python bench.py --full --no-cpu "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
 for v in 0 1; do
   run rt16_s$v RONK_SMALL=$v --workload roundtrip16 --steps 400 --warmup 40
   for lg in 13 14 15 17; do run rt${lg}_s$v RONK_SMALL=$v --workload roundtrip16 --log2n $lg --steps 400 --warmup 40; done

@@ -1,6 +1,6 @@
 O=gpurun_out/r02ae; mkdir -p $O
 run() { local name=$1; local envs=$2; shift 2
-  env $envs timeout 120 python bench.py --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
+  env $envs timeout 120 python bench.py --full --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
 for v in 0 1; do
   for lg in 18 19 20; do run f${lg}_s$v RONK_SMALL=$v --workload batch16 --log2n $lg --batch 1 --steps 400 --warmup 40; done
   run f16x8_s$v RONK_SMALL=$v --workload batch16 --log2n 16 --batch 8 --steps 400 --warmup 40

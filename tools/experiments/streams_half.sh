@@ -1,6 +1,6 @@
 O=gpurun_out/r02ah; mkdir -p $O
 run() { local name=$1; local envs=$2; shift 2
-  env $envs timeout 120 python bench.py --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
+  env $envs timeout 120 python bench.py --full --no-cpu --no-verify "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
 run s2_c2_h0 RONK_HALF_LDS=0 --streams 2 --tile-logc 2 --steps 300 --warmup 30
 for s in 2 3 4 6; do for c in 2 3; do
   run s${s}_c${c}_h1 RONK_HALF_LDS=1 --streams $s --tile-logc $c --steps 300 --warmup 30

@@ -1,6 +1,6 @@
 O=gpurun_out/r02ab; mkdir -p $O
 run() { local name=$1; local envs=$2; shift 2
-  env $envs timeout 120 python bench.py --no-cpu "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
+  env $envs timeout 120 python bench.py --full --no-cpu "$@" > $O/$name.json 2>> $O/err || echo "FAIL $name" >> $O/err; }
 for m in 0 16 32 64 128 192; do
   run b16_m$m RONK_SUB_BATCH_MIB=$m --workload batch16 --steps 50 --warmup 10
 done

@@ -3,7 +3,7 @@
 # round's evidence run re-read on the FINAL library in a few minutes.  One compact table on stdout, the JSON lines under <outdir>.
 OUT=${1:-gpurun_out/final_lines}
 mkdir -p $OUT
-run() { name=$1; shift; timeout 300 python bench.py "$@" 2>> $OUT/err | tail -1 > $OUT/$name.json; }
+run() { name=$1; shift; timeout 300 python bench.py --full "$@" 2>> $OUT/err | tail -1 > $OUT/$name.json; }
 run ntt22_driver_args --gpus 1 --steps 20 --warmup 5
 run ntt22_default
 run ntt22_1stream --no-cpu --mode streams --streams 1

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --workload $WL --steps 100 --warmup 10 --samples 1 --no-cpu --no-verify $*"
+CMD="python $ROOT/bench.py --full --workload $WL --steps 100 --warmup 10 --samples 1 --no-cpu --no-verify $*"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -- $CMD > $OUT/trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -- $CMD > $OUT/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -- $CMD > $OUT/write.log 2>&1

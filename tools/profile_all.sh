@@ -25,25 +25,25 @@ prof mul22 mul22 -
 prof open22 open22 latest_pmc_open22.json
 prof eval22 eval22 latest_pmc_eval22.json
 cp profiles/latest_pmc_*.json $OUT/
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/err
-timeout 300 python bench.py > $OUT/bench_default.json 2>> $OUT/err
-timeout 200 python bench.py --no-cpu --mode streams --streams 1 > $OUT/bench_ntt22_1stream.json 2>> $OUT/err
-timeout 200 python bench.py --no-cpu --mode streams --streams 2 > $OUT/bench_ntt22_2streams.json 2>> $OUT/err
-timeout 200 python bench.py --no-cpu --mode batch --group 16 > $OUT/bench_ntt22_batch16.json 2>> $OUT/err
-timeout 300 python bench.py --prime 0xFFFFFFFC00000001 --steps 20 --warmup 5 > $OUT/bench_mont_driver_args.json 2>> $OUT/err
-timeout 200 python bench.py --no-cpu --prime 0xFFFFFFFC00000001 --mode streams --streams 1 > $OUT/bench_mont_1stream.json 2>> $OUT/err
-timeout 200 python bench.py --no-cpu --prime 0x3a00000000000001 > $OUT/bench_mont_29x2p57.json 2>> $OUT/err
-for wl in mul22 batch16 roundtrip16; do timeout 300 python bench.py --no-cpu --workload $wl --prime 0xFFFFFFFC00000001 > $OUT/bench_mont_$wl.json 2>> $OUT/err; done
-for wl in batch16 mul22 roundtrip16 rs16; do timeout 300 python bench.py --workload $wl > $OUT/bench_$wl.json 2>> $OUT/err; done
-for wl in open22 eval22 vecmul24 vecadd24; do timeout 100 python bench.py --no-cpu --workload $wl > $OUT/bench_$wl.json 2>> $OUT/err; done
-timeout 300 python bench.py --workload e2e22 --steps 64 --samples 3 > $OUT/bench_e2e22.json 2>> $OUT/err
-for lg in 16 20; do timeout 300 python bench.py --workload msm20 --log2n $lg --steps 5 --samples 3 > $OUT/bench_msm$lg.json 2>> $OUT/err; done
-for lg in 20 21 23 24 26; do timeout 150 python bench.py --no-cpu --mode streams --streams 1 --log2n $lg --steps 40 --warmup 5 --samples 3 > $OUT/bench_ntt$lg.json 2>> $OUT/err; done
-timeout 100 python bench.py --no-cpu --workload fourstep --log2n 26 --steps 20 --warmup 3 > $OUT/bench_fourstep_1gpu.json 2>> $OUT/err
-timeout 100 python bench.py --no-cpu --workload sharded --ranks 8 --log2n 26 --steps 20 --warmup 3 > $OUT/bench_sharded_8ranks_1gpu.json 2>> $OUT/err
+timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/err
+timeout 300 python bench.py --full > $OUT/bench_default.json 2>> $OUT/err
+timeout 200 python bench.py --full --no-cpu --mode streams --streams 1 > $OUT/bench_ntt22_1stream.json 2>> $OUT/err
+timeout 200 python bench.py --full --no-cpu --mode streams --streams 2 > $OUT/bench_ntt22_2streams.json 2>> $OUT/err
+timeout 200 python bench.py --full --no-cpu --mode batch --group 16 > $OUT/bench_ntt22_batch16.json 2>> $OUT/err
+timeout 300 python bench.py --full --prime 0xFFFFFFFC00000001 --steps 20 --warmup 5 > $OUT/bench_mont_driver_args.json 2>> $OUT/err
+timeout 200 python bench.py --full --no-cpu --prime 0xFFFFFFFC00000001 --mode streams --streams 1 > $OUT/bench_mont_1stream.json 2>> $OUT/err
+timeout 200 python bench.py --full --no-cpu --prime 0x3a00000000000001 > $OUT/bench_mont_29x2p57.json 2>> $OUT/err
+for wl in mul22 batch16 roundtrip16; do timeout 300 python bench.py --full --no-cpu --workload $wl --prime 0xFFFFFFFC00000001 > $OUT/bench_mont_$wl.json 2>> $OUT/err; done
+for wl in batch16 mul22 roundtrip16 rs16; do timeout 300 python bench.py --full --workload $wl > $OUT/bench_$wl.json 2>> $OUT/err; done
+for wl in open22 eval22 vecmul24 vecadd24; do timeout 100 python bench.py --full --no-cpu --workload $wl > $OUT/bench_$wl.json 2>> $OUT/err; done
+timeout 300 python bench.py --full --workload e2e22 --steps 64 --samples 3 > $OUT/bench_e2e22.json 2>> $OUT/err
+for lg in 16 20; do timeout 300 python bench.py --full --workload msm20 --log2n $lg --steps 5 --samples 3 > $OUT/bench_msm$lg.json 2>> $OUT/err; done
+for lg in 20 21 23 24 26; do timeout 150 python bench.py --full --no-cpu --mode streams --streams 1 --log2n $lg --steps 40 --warmup 5 --samples 3 > $OUT/bench_ntt$lg.json 2>> $OUT/err; done
+timeout 100 python bench.py --full --no-cpu --workload fourstep --log2n 26 --steps 20 --warmup 3 > $OUT/bench_fourstep_1gpu.json 2>> $OUT/err
+timeout 100 python bench.py --full --no-cpu --workload sharded --ranks 8 --log2n 26 --steps 20 --warmup 3 > $OUT/bench_sharded_8ranks_1gpu.json 2>> $OUT/err
 # the multi-rank control flow of bench.py (two ranks sharing this GPU over gloo: a smoke test of --gpus N, not a measurement)
-RONK_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu > $OUT/bench_2ranks_gloo_smoke.json 2>> $OUT/err
-RONK_BENCH_BACKEND=gloo timeout 300 python bench.py --gpus 2 --workload fourstep --log2n 24 --steps 10 --warmup 2 --no-cpu > $OUT/bench_fourstep_2ranks_gloo_smoke.json 2>> $OUT/err
+RONK_BENCH_BACKEND=gloo timeout 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-cpu > $OUT/bench_2ranks_gloo_smoke.json 2>> $OUT/err
+RONK_BENCH_BACKEND=gloo timeout 300 python bench.py --full --gpus 2 --workload fourstep --log2n 24 --steps 10 --warmup 2 --no-cpu > $OUT/bench_fourstep_2ranks_gloo_smoke.json 2>> $OUT/err
 timeout 300 python tools/mul_sizes.py > $OUT/mul_sizes.txt 2>> $OUT/err
 FUZZ_SEED=51 FUZZ_SECONDS=150 timeout 400 python tools/fuzz_gpu.py mont ntt mul > $OUT/fuzz_mont.txt 2>&1
 FUZZ_SEED=61 FUZZ_SECONDS=200 timeout 500 python tools/fuzz_gpu.py lindiv divrem vec sharded > $OUT/fuzz_callers.txt 2>&1

@@ -18,11 +18,11 @@ prof ntt22 ntt22_mont latest_pmc_ntt22_mont.json --prime 0xFFFFFFFC00000001
 prof batch16 batch16 latest_pmc_batch16.json
 prof mul22 mul22 -
 cp profiles/latest_pmc_*.json $OUT/
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/err
-timeout 300 python bench.py > $OUT/bench_default.json 2>> $OUT/err
-timeout 200 python bench.py --no-cpu --mode streams --streams 1 > $OUT/bench_ntt22_1stream.json 2>> $OUT/err
-timeout 300 python bench.py --prime 0xFFFFFFFC00000001 --steps 20 --warmup 5 > $OUT/bench_mont_driver_args.json 2>> $OUT/err
-for wl in batch16 mul22; do timeout 300 python bench.py --no-cpu --workload $wl > $OUT/bench_$wl.json 2>> $OUT/err; done
+timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/err
+timeout 300 python bench.py --full > $OUT/bench_default.json 2>> $OUT/err
+timeout 200 python bench.py --full --no-cpu --mode streams --streams 1 > $OUT/bench_ntt22_1stream.json 2>> $OUT/err
+timeout 300 python bench.py --full --prime 0xFFFFFFFC00000001 --steps 20 --warmup 5 > $OUT/bench_mont_driver_args.json 2>> $OUT/err
+for wl in batch16 mul22; do timeout 300 python bench.py --full --no-cpu --workload $wl > $OUT/bench_$wl.json 2>> $OUT/err; done
 python - <<PY
 import json,glob
 for f in sorted(glob.glob('$OUT/bench_*.json')):
