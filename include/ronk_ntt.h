@@ -409,6 +409,35 @@ int ronk_sharded_sync(ronk_sharded_plan* plan);
 /* host pointers, natural order in and out (n elements each): scatter, transform, gather; synchronous */
 int ronk_ntt_sharded(ronk_sharded_plan* plan, const uint64_t* in, uint64_t* out);
 
+/* ---- the sharded polynomial multiply (reference `impl Mul`, src/polynomial/arithmetic.rs:97-119, at a size sharded over the
+ *      node): same devices, chunks, exchange and field arguments as ronk_sharded_plan_create_p.  Per rank: forward phase 1 of a
+ *      and b, exchange, a MIDDLE (forward phase 2 of both, pointwise product, phase 1 of an inverse whose split is the forward's
+ *      swapped), exchange, inverse phase 2.  The forward's output block is the swapped inverse's input block, so the product
+ *      comes back in the operands' own layout.  The middle is one fused kernel per inverse column chunk where an instantiation
+ *      exists (log2n 18 .. 25, ndev * chunks >= 16) and it measured faster (by default log2n = 24; RONK_SHARDED_MUL_FUSED: wherever
+ *      it exists); otherwise forward phase 2 writes both spectra and the inverse's phase 1 multiplies them on load.  Errors as for ronk_sharded_plan_create_p (both splits must be valid shapes). */
+typedef struct ronk_sharded_mul_plan ronk_sharded_mul_plan;
+#define RONK_SHARDED_MUL_UNFUSED 1   /* the composed middle */
+#define RONK_SHARDED_MUL_FUSED 2     /* the fused middle wherever an instantiation matches (A/B; default: only where it measured faster) */
+int ronk_sharded_mul_plan_create_p(ronk_sharded_mul_plan** out, uint64_t p, uint64_t g, uint32_t log2n, const int* devices,
+                                   int ndev, int chunks, int exchange, int flags);
+/* Goldilocks shorthand */
+int ronk_sharded_mul_plan_create(ronk_sharded_mul_plan** out, uint32_t log2n, const int* devices, int ndev, int chunks,
+                                 int exchange, int flags);
+/* R, C, n / ndev, chunks in use, and whether the plan runs the fused middle (1) or the composed one (0); pointers may be NULL */
+int ronk_sharded_mul_plan_info(const ronk_sharded_mul_plan* plan, uint64_t* rows, uint64_t* cols, uint64_t* per_rank,
+                               int* chunks, int* fused_middle);
+int ronk_sharded_mul_plan_destroy(ronk_sharded_mul_plan* plan);
+/* d_a[g], d_b[g], d_out[g]: rank g's [R][C/ndev] column block of the zero-padded n-point vectors (the layout of
+ * ronk_ntt_sharded_dev's input); d_out comes back in the same layout.  Computes the length-n CYCLIC convolution, which is a * b
+ * when d + d2 - 1 <= n.  Enqueue-only on the plan's streams; successive calls pipeline; d_out[g] may be an input of the next
+ * call (chaining), but not an input of the same call. */
+int ronk_poly_mul_sharded_dev(ronk_sharded_mul_plan* plan, const uint64_t* const* d_a, const uint64_t* const* d_b,
+                              uint64_t* const* d_out);
+int ronk_sharded_mul_sync(ronk_sharded_mul_plan* plan);
+/* host pointers: a (d coefficients), b (d2) -> out (d + d2 - 1) = ronk_poly_mul; d + d2 - 1 > n is RONK_ERR_INVALID; synchronous */
+int ronk_poly_mul_sharded(ronk_sharded_mul_plan* plan, const uint64_t* a, size_t d, const uint64_t* b, size_t d2, uint64_t* out);
+
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);
 int ronk_dev_free(void* ptr);

@@ -135,6 +135,13 @@ _SIG = {
     "ronk_ntt_sharded_dev": (_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "ronk_sharded_sync": (_int, [_vp]),
     "ronk_ntt_sharded": (_int, [_vp, _vp, _vp]),
+    "ronk_sharded_mul_plan_create_p": (_int, [C.POINTER(_vp), _u64, _u64, C.c_uint32, C.POINTER(_int), _int, _int, _int, _int]),
+    "ronk_sharded_mul_plan_create": (_int, [C.POINTER(_vp), C.c_uint32, C.POINTER(_int), _int, _int, _int, _int]),
+    "ronk_sharded_mul_plan_info": (_int, [_vp, _pu, _pu, _pu, C.POINTER(_int), C.POINTER(_int)]),
+    "ronk_sharded_mul_plan_destroy": (_int, [_vp]),
+    "ronk_poly_mul_sharded_dev": (_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "ronk_sharded_mul_sync": (_int, [_vp]),
+    "ronk_poly_mul_sharded": (_int, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "ronk_dev_alloc": (_int, [C.POINTER(_vp), _sz]),
     "ronk_dev_free": (_int, [_vp]),
     "ronk_memcpy_h2d": (_int, [_vp, _vp, _sz]),
@@ -324,6 +331,57 @@ class ShardedPlan:
     def close(self):
         if getattr(self, "h", None):
             lib.ronk_sharded_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if lib is not None:
+            self.close()
+
+
+SHARDED_MUL_UNFUSED, SHARDED_MUL_FUSED = 1, 2
+
+
+class ShardedMulPlan:
+    """ronk_sharded_mul_plan: a * b over `devices` (the polynomial product sharded like ShardedPlan's transform).  Operands and
+    product share the [R][C/W] column-block layout per rank (dist.scatter_input); `fused_middle` says whether the plan runs the
+    fused middle kernel (1) or the composed one (0).  unfused=True forces the composed middle (RONK_SHARDED_MUL_UNFUSED), fused=True
+    the fused one wherever an instantiation matches (RONK_SHARDED_MUL_FUSED); default: the library's measured choice."""
+
+    def __init__(self, log2n, devices, chunks=0, exchange=EXCHANGE_MESH, p=None, g=None, unfused=False, fused=False):
+        self.h = None
+        h = _vp()
+        devs = (_int * len(devices))(*devices)
+        flags = (SHARDED_MUL_UNFUSED if unfused else 0) | (SHARDED_MUL_FUSED if fused else 0)
+        if p is None:
+            check(lib.ronk_sharded_mul_plan_create(C.byref(h), log2n, devs, len(devices), chunks, exchange, flags))
+        else:
+            check(lib.ronk_sharded_mul_plan_create_p(C.byref(h), int(p), int(g), log2n, devs, len(devices), chunks, exchange, flags))
+        self.exchange = exchange
+        self.h, self.n, self.ndev = h, 1 << log2n, len(devices)
+        r, c, per, ch, fu = _u64(0), _u64(0), _u64(0), _int(0), _int(0)
+        check(lib.ronk_sharded_mul_plan_info(h, C.byref(r), C.byref(c), C.byref(per), C.byref(ch), C.byref(fu)))
+        self.R, self.C, self.per_rank, self.chunks, self.fused_middle = r.value, c.value, per.value, ch.value, fu.value
+
+    def mul(self, a, b):
+        """host coefficient vectors of any lengths with len(a) + len(b) - 1 <= n -> their product (ronk_poly_mul_sharded)"""
+        a, b = arr(a), arr(b)
+        out = np.empty(a.size + b.size - 1, dtype=np.uint64)
+        check(lib.ronk_poly_mul_sharded(self.h, ptr(a), a.size, ptr(b), b.size, ptr(out)))
+        return out
+
+    def mul_dev(self, d_a, d_b, d_out):
+        """device pointers per rank (lists of ints), [R][C/W] blocks of the zero-padded n-point vectors; asynchronous, see sync()"""
+        a = (_vp * self.ndev)(*d_a)
+        b = (_vp * self.ndev)(*d_b)
+        o = (_vp * self.ndev)(*d_out)
+        check(lib.ronk_poly_mul_sharded_dev(self.h, a, b, o))
+
+    def sync(self):
+        check(lib.ronk_sharded_mul_sync(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.ronk_sharded_mul_plan_destroy(self.h)
             self.h = None
 
     def __del__(self):

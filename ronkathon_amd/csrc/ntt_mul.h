@@ -79,4 +79,15 @@ inline bool mul_mid_matches(const TileArgs& fa, const TileArgs& ia, int logr, in
          tile_cfg_matches(ia, logr, logc, kindi);
 }
 
+// The sharded multiply's middle (ronk_dist.hip): fa = forward phase 2 over the operand pair (receive buffer, rows in blocks of
+// 2^js_log, batch of two), ia = phase 1 of the swapped-split inverse (KIND 4: global twiddle with the rank's column offset,
+// n^-1 folded in).  One tile of each: the same C local k1 columns, every k2.  The forward side must be a KIND 2 row pass: its
+// blocks of 2^js_log = C / (W * chunks) received rows no longer than a lane's row step C/16, i.e. W * chunks >= 16.
+inline bool mul_mid_matches_dist(const TileArgs& fa, const TileArgs& ia, int logr, int logc) {
+  const u64 C = (u64)1 << logc;
+  return fa.nb1 == 2 && fa.nb2 == 1 && ia.nb1 == 1 && ia.nb2 == 1 && fa.tiles == ia.tiles && fa.logc == (u32)logc &&
+         ia.logc == (u32)logc && tile_features(fa) == 0 && tile_features(ia) == 0 && fa.ncols == (u64)fa.tiles * C &&
+         tile_cfg_matches(fa, logr, logc, 2) && tile_cfg_matches(ia, logr, logc, 4);
+}
+
 }  // namespace ronk

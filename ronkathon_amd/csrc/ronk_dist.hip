@@ -9,6 +9,8 @@
 #include <chrono>
 
 #include "runtime.h"
+#include "ntt_mul.h"
+#include "plan_dist_mul.h"
 
 // The field of a four-step plan: Goldilocks with the reference-convention generator 7 (the shift-twiddle kernels), or any odd
 // prime p < 2^64 with n | p - 1 whose g is a quadratic non-residue -- omega_n = g^((p-1)/n) then has order exactly n and the
@@ -177,6 +179,11 @@ struct ShardRank {
   hipEvent_t done = nullptr;                       // phase 2 has read the receive buffer
   rcclComm_t comm = nullptr;
   bool used = false;
+  // sharded multiply only (ronk_sharded_mul_plan): p1 / p2 are then the forward phases of the operand pair (send, recv and tmp hold
+  // two polynomials), q1 / q2 the phases of the swapped-split inverse with their own exchange buffers, spec the two spectra of
+  // the composed middle
+  CompiledPlan q1, q2;
+  u64 *spec = nullptr, *send2 = nullptr, *recv2 = nullptr;
 };
 struct ronk_sharded_plan {
   DistShape sh;
@@ -206,8 +213,8 @@ extern "C" int ronk_sharded_plan_destroy(ronk_sharded_plan* pl) {
   for (auto& k : pl->r) {
     (void)hipSetDevice(k.device);
     if (k.comm && g_rccl.ok) (void)g_rccl.CommDestroy(k.comm);
-    k.p1.release(); k.p2.release();
-    for (u64* q : {k.tmp, k.send, k.recv, k.stage_in, k.stage_out}) if (q) (void)hipFree(q);
+    k.p1.release(); k.p2.release(); k.q1.release(); k.q2.release();
+    for (u64* q : {k.tmp, k.send, k.recv, k.stage_in, k.stage_out, k.spec, k.send2, k.recv2}) if (q) (void)hipFree(q);
     for (auto e : k.chunk_done) if (e) (void)hipEventDestroy(e);
     for (auto e : k.sent_to) if (e) (void)hipEventDestroy(e);
     if (k.done) (void)hipEventDestroy(k.done);
@@ -229,15 +236,25 @@ extern "C" int ronk_sharded_plan_create_ex(ronk_sharded_plan** out, uint32_t log
                                            int chunks, int exchange) {
   return ronk_sharded_plan_create_p(out, RONK_GOLDILOCKS_P, RONK_GOLDILOCKS_G, log2n, inverse, devices, ndev, chunks, exchange);
 }
+// mul: the resources of a sharded multiply (ronk_sharded_mul_plan below) instead of a transform's; `inverse` is then ignored
+static int sharded_create(ronk_sharded_plan** out, uint64_t p, uint64_t g, uint32_t log2n, int inverse, const int* devices,
+                          int ndev, int chunks, int exchange, bool mul, bool want_fused, bool* fused);
 extern "C" int ronk_sharded_plan_create_p(ronk_sharded_plan** out, uint64_t p, uint64_t g, uint32_t log2n, int inverse,
                                           const int* devices, int ndev, int chunks, int exchange) {
+  return sharded_create(out, p, g, log2n, inverse, devices, ndev, chunks, exchange, false, false, nullptr);
+}
+static bool mul_mid_fusable(const ShardRank& k, const DistShape& ish, int chunks);
+static int sharded_create(ronk_sharded_plan** out, uint64_t p, uint64_t g, uint32_t log2n, int inverse, const int* devices,
+                          int ndev, int chunks, int exchange, bool mul, bool want_fused, bool* fused) {
   if (!out || !devices || ndev < 1) return RONK_ERR_INVALID;
   if (exchange != RONK_EXCHANGE_MESH && exchange != RONK_EXCHANGE_RCCL) return RONK_ERR_INVALID;
   *out = nullptr;
   HostField hf;
   RCHK(dist_field(p, g, log2n, &hf));
-  DistShape sh;
+  DistShape sh, ish;
   if (!dist_shape((int)log2n, ndev, &sh)) return RONK_ERR_UNSUPPORTED;
+  if (mul && !dist_shape_mul((int)log2n, ndev, &ish, true)) return RONK_ERR_UNSUPPORTED;   // the inverse's swapped split
+  auto chunks_ok = [&](int c) { return dist_chunks_ok(sh, c) && (!mul || dist_chunks_ok(ish, c)); };
   RCHK(need_device());
   int ndevices = 0;
   HIPCHK(hipGetDeviceCount(&ndevices));
@@ -251,16 +268,17 @@ extern "C" int ronk_sharded_plan_create_p(ronk_sharded_plan** out, uint64_t p, u
   }
   if (chunks <= 0) {   // default: up to 4 chunks (the exchange of chunk j hides under chunks j+1 ..)
     chunks = 4;
-    while (chunks > 1 && !dist_chunks_ok(sh, chunks)) chunks >>= 1;
+    while (chunks > 1 && !chunks_ok(chunks)) chunks >>= 1;
   }
-  if (!dist_chunks_ok(sh, chunks)) return RONK_ERR_UNSUPPORTED;
+  if (!chunks_ok(chunks)) return RONK_ERR_UNSUPPORTED;
   int prev = 0;
   HIPCHK(hipGetDevice(&prev));
   ronk_sharded_plan* pl = new ronk_sharded_plan();
   pl->sh = sh; pl->ndev = ndev; pl->chunks = chunks; pl->inverse = inverse != 0; pl->exchange = exchange;
   pl->r.resize(ndev);
   pl->peer.assign((size_t)ndev * ndev, RONK_PEER_SAME_DEVICE);
-  const size_t per = (size_t)(sh.n / sh.W);
+  const size_t per = (size_t)(sh.n / sh.W), nb = mul ? 2 : 1;   // polynomials per forward buffer
+  if (fused) *fused = false;
   const int ncopy = exchange == RONK_EXCHANGE_RCCL ? 1 : ndev;
   int rc = RONK_OK;
   for (int g = 0; g < ndev && !rc; g++) {
@@ -290,13 +308,23 @@ extern "C" int ronk_sharded_plan_create_p(ronk_sharded_plan** out, uint64_t p, u
       how = pe == hipSuccess ? RONK_PEER_DIRECT : RONK_PEER_STAGED;
     }
     if (!rc) rc = k.p1.compile(build_dist_phase1((int)log2n, inverse != 0, g, ndev, 4, 0, 0, chunks, hf));
-    if (!rc) rc = k.p2.compile(build_dist_phase2((int)log2n, inverse != 0, g, ndev, 4, 0, chunks, hf));
+    if (!rc) rc = k.p2.compile(mul ? build_dist_mul_phase2((int)log2n, false, g, ndev, 4, 0, chunks, hf, false, 2)   // the pair
+                                   : build_dist_phase2((int)log2n, inverse != 0, g, ndev, 4, 0, chunks, hf));
     if (!rc && (k.p1.pd.passes.empty() || k.p2.pd.passes.empty())) rc = RONK_ERR_UNSUPPORTED;
+    if (mul) {   // the inverse with the split swapped: n^-1 folded into its phase 1's global twiddle as for any inverse
+      if (!rc) rc = k.q1.compile(build_dist_mul_phase1((int)log2n, true, g, ndev, 4, 0, 0, chunks, hf, true));
+      if (!rc) rc = k.q2.compile(build_dist_mul_phase2((int)log2n, true, g, ndev, 4, 0, chunks, hf, true));
+      if (!rc && (k.q1.pd.passes.empty() || k.q2.pd.passes.empty())) rc = RONK_ERR_UNSUPPORTED;
+      if (!rc && g == 0 && fused) *fused = want_fused && mul_mid_fusable(k, ish, chunks);
+    }
     hipError_t e = hipSuccess;
     if (!rc) e = hipStreamSynchronize(0);   // the table uploads (null-stream copies) before the plan's non-blocking streams use them
-    if (!rc) e = hipMalloc((void**)&k.tmp, per * 8);
-    if (!rc && e == hipSuccess) e = hipMalloc((void**)&k.send, per * 8);
-    if (!rc && e == hipSuccess) e = hipMalloc((void**)&k.recv, per * 8);
+    if (!rc) e = hipMalloc((void**)&k.tmp, nb * per * 8);
+    if (!rc && e == hipSuccess) e = hipMalloc((void**)&k.send, nb * per * 8);
+    if (!rc && e == hipSuccess) e = hipMalloc((void**)&k.recv, nb * per * 8);
+    if (mul && !rc && e == hipSuccess) e = hipMalloc((void**)&k.send2, per * 8);
+    if (mul && !rc && e == hipSuccess) e = hipMalloc((void**)&k.recv2, per * 8);
+    if (mul && !rc && e == hipSuccess && !(fused && *fused)) e = hipMalloc((void**)&k.spec, nb * per * 8);
     if (!rc && e == hipSuccess) e = hipStreamCreateWithFlags(&k.compute, hipStreamNonBlocking);
     // mesh: one copy stream per destination DEVICE (= per xGMI link, plus one for blocks that stay on this device); logical
     // ranks that share a GPU share the stream -- there is one link to keep busy, and every extra stream costs queue switches
@@ -578,5 +606,259 @@ extern "C" int ronk_ntt_sharded(ronk_sharded_plan* pl, const uint64_t* in, uint6
     }
   }
   (void)hipSetDevice(prev);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------ sharded polynomial multiply, single process
+// a * b = iNTT(NTT(a) . NTT(b)) over the node (reference `impl Mul`, src/polynomial/arithmetic.rs:97-119).  Forward:
+// n = R*C, rank g holds [R][C/W] of each operand and ends phase 2 with X[k1 + R*k2] as [C][R/W] (k1 in its block).  The inverse is
+// built with the split SWAPPED (R' = C, C' = R: plan.h dist_shape(swapped)): its input layout [R'][C'/W] is that very block
+// (r' = k2, c' = k1), so nothing is redistributed between the two transforms, and its output [C'][R'/W] is the column block of
+// the forward split -- the product comes back in the operands' layout.  Between the two exchanges the rank-local work is forward
+// phase 2 (C-point lines along k2, per local k1) and inverse phase 1 (R' = C-point lines along the same k2, per local k1): the
+// F2 -> I1 tile relation of the single-GPU fused multiply (ntt_mul.h), run as ONE kernel per inverse column chunk.
+//   compute_g : [fwd phase 1 of a, b per chunk] (wait: fwd blocks to g) [middle per inverse chunk] (wait: inv blocks to g) [inv phase 2]
+//   copy_g[h] :      fwd chunk j -> h (a and b)                               inv chunk j -> h
+// The transform plan's machinery throughout (ShardRank: streams, events, peer table, RCCL communicators); its cross-call guards
+// cover both exchanges (sent_to / done are recorded after the second one).
+struct ronk_sharded_mul_plan {
+  ronk_sharded_plan* sp = nullptr;   // p1 / p2 = forward phases of the pair, q1 / q2 = the swapped inverse (ShardRank)
+  DistShape ish;                     // the inverse's split
+  bool fused = false;
+};
+
+// the launch arguments of the fused middle for inverse column chunk j of rank k: the forward row pass restricted to the chunk's
+// local k1 columns, the inverse's phase 1 shifted to the chunk like CompiledPlan::launch does (x0_add, output piece)
+static void mul_mid_args(const ShardRank& k, const DistShape& ish, int chunks, int j, TileArgs* fa, TileArgs* ia) {
+  const u64 cc = ish.Cw / (u64)chunks;
+  *fa = k.p2.bound(0, k.recv, nullptr, nullptr, k.tmp);
+  *ia = k.q1.bound(0, nullptr, nullptr, k.send2, k.tmp);
+  fa->in += (i64)((u64)j * cc) * fa->in_sc;
+  fa->ncols = cc;
+  fa->tiles = (u32)(cc >> fa->logc);
+  ia->x0 += (u64)j * cc * ia->xc;
+  if (ia->out) ia->out += (u64)j * ish.R * cc;
+}
+static bool mul_mid_fusable(const ShardRank& k, const DistShape& ish, int chunks) {
+  if (k.p2.pd.passes.size() != 1 || k.q1.pd.passes.size() != 1) return false;
+  const PassDesc& fp = k.p2.pd.passes[0];
+  TileArgs fa, ia;
+  mul_mid_args(k, ish, chunks, 0, &fa, &ia);
+  return !fp.small && !k.q1.pd.passes[0].small && fp.logr == k.q1.pd.passes[0].logr && fp.block == k.q1.pd.passes[0].block &&
+         mul_mid_matches_dist(fa, ia, fp.logr, (int)fa.logc) && mul_mid_dist_available(fp.logr, (int)fa.logc);
+}
+
+// One exchange of the multiply with the chunk schedule of sharded_enqueue: compute(g, j) enqueues rank g's chunk j on its compute
+// stream, which writes `npoly` polynomials (n/W elements apart) of `rows` x cwc into the send buffer at j*rows*cwc; block h of each
+// goes to rank h's receive buffer at (g*chunks + j)*blk.  second: the inverse's buffers (send2 / recv2).
+template <class F>
+static int mul_exchange(ronk_sharded_plan* pl, u64 rows, u64 cwc, int npoly, bool second, F&& compute) {
+  const int W = pl->ndev, chunks = pl->chunks;
+  const bool rccl = pl->exchange == RONK_EXCHANGE_RCCL;
+  const u64 per = pl->sh.n / pl->sh.W, blk = rows / (u64)W * cwc;
+  bool one_device = !rccl;
+  for (int g = 1; g < W; g++) one_device = one_device && pl->r[g].device == pl->r[0].device;
+  const int outer = one_device ? W : chunks, inner = one_device ? chunks : W;
+  for (int o = 0; o < outer; o++) {
+    for (int i = 0; i < inner; i++) {
+      const int j = one_device ? i : o, g = one_device ? o : i;
+      ShardRank& k = pl->r[g];
+      RCHK(on_device(k.device));
+      RCHK(compute(g, j));
+      HIPCHK(hipEventRecord(k.chunk_done[j], k.compute));
+      if (rccl) { HIPCHK(hipStreamWaitEvent(k.copy[0], k.chunk_done[j], 0)); continue; }
+      const u64* piece = (second ? k.send2 : k.send) + (u64)j * rows * cwc;
+      for (int hh = 0; hh < W; hh++) {
+        const int h = (g + hh) % W;
+        HIPCHK(hipStreamWaitEvent(k.copy[h], k.chunk_done[j], 0));
+        for (int b1 = 0; b1 < npoly; b1++) {
+          u64* dst = (second ? pl->r[h].recv2 : pl->r[h].recv) + (u64)b1 * per + ((u64)g * chunks + j) * blk;
+          const u64* src = piece + (u64)b1 * per + (u64)h * blk;
+          if (pl->peer[(size_t)g * W + h] == RONK_PEER_SAME_DEVICE) HIPCHK(hipMemcpyAsync(dst, src, blk * 8, hipMemcpyDeviceToDevice, k.copy[h]));
+          else HIPCHK(hipMemcpyPeerAsync(dst, pl->r[h].device, src, k.device, blk * 8, k.copy[h]));
+        }
+      }
+    }
+    if (rccl) {
+      const int j = o;
+      RCCLCHK(g_rccl.GroupStart());
+      int r_ = 0;
+      for (int g = 0; g < W && !r_; g++) {
+        ShardRank& k = pl->r[g];
+        const u64* piece = (second ? k.send2 : k.send) + (u64)j * rows * cwc;
+        u64* recv = second ? k.recv2 : k.recv;
+        for (int h = 0; h < W && !r_; h++)
+          for (int b1 = 0; b1 < npoly && !r_; b1++) {
+            r_ = g_rccl.Send(piece + (u64)b1 * per + (u64)h * blk, (size_t)blk, kNcclUint64, h, k.comm, k.copy[0]);
+            if (!r_) r_ = g_rccl.Recv(recv + (u64)b1 * per + ((u64)h * chunks + j) * blk, (size_t)blk, kNcclUint64, h, k.comm, k.copy[0]);
+          }
+      }
+      const int r2 = g_rccl.GroupEnd();
+      if (r_) return rccl_fail(r_, "ncclSend / ncclRecv");
+      if (r2) return rccl_fail(r2, "ncclGroupEnd");
+    }
+  }
+  for (int g = 0; g < W; g++) {
+    ShardRank& k = pl->r[g];
+    RCHK(on_device(k.device));
+    for (size_t h = 0; h < k.copy.size(); h++) HIPCHK(hipEventRecord(k.sent_to[h], k.copy[h]));
+  }
+  return RONK_OK;
+}
+// rank h's compute stream waits until every rank's blocks for h (of the exchange just enqueued) have landed
+static int mul_wait_received(ronk_sharded_plan* pl, int h) {
+  const bool rccl = pl->exchange == RONK_EXCHANGE_RCCL;
+  for (int g = 0; g < pl->ndev; g++) HIPCHK(hipStreamWaitEvent(pl->r[h].compute, pl->r[g].sent_to[rccl ? 0 : h], 0));
+  return RONK_OK;
+}
+
+static int mul_enqueue(ronk_sharded_mul_plan* mp, const uint64_t* const* d_a, const uint64_t* const* d_b, uint64_t* const* d_out) {
+  ronk_sharded_plan* pl = mp->sp;
+  const DistShape& sh = pl->sh;
+  const DistShape& ish = mp->ish;
+  const int W = pl->ndev, chunks = pl->chunks;
+  const bool rccl = pl->exchange == RONK_EXCHANGE_RCCL;
+  const u64 per = sh.n / sh.W, Cwc = sh.Cw / (u64)chunks, cc = ish.Cw / (u64)chunks;
+  // buffer reuse across calls (as sharded_enqueue; sent_to / done of the previous call were recorded after its second exchange)
+  for (int g = 0; g < W; g++) {
+    ShardRank& k = pl->r[g];
+    if (!k.used) continue;
+    RCHK(on_device(k.device));
+    for (auto ev : k.sent_to) HIPCHK(hipStreamWaitEvent(k.compute, ev, 0));
+    if (rccl) { for (int h = 0; h < W; h++) HIPCHK(hipStreamWaitEvent(k.copy[0], pl->r[h].done, 0)); }
+    else for (int h = 0; h < W; h++) HIPCHK(hipStreamWaitEvent(k.copy[h], pl->r[h].done, 0));
+  }
+  // forward phase 1 of a and b, first exchange (both operands' blocks)
+  RCHK(mul_exchange(pl, sh.R, Cwc, 2, false, [&](int g, int j) {
+    ShardRank& k = pl->r[g];
+    u64* piece = k.send + (u64)j * sh.R * Cwc;
+    RCHK(k.p1.run(d_a[g] + (u64)j * Cwc, nullptr, piece, k.tmp, k.compute, ~(u64)0, ~(u64)0, 0, (u64)j * Cwc));
+    return k.p1.run(d_b[g] + (u64)j * Cwc, nullptr, piece + per, k.tmp, k.compute, ~(u64)0, ~(u64)0, 0, (u64)j * Cwc);
+  }));
+  // the middle.  Composed: forward phase 2 writes both spectra, the inverse's phase 1 multiplies them on load (TileArgs::in2)
+  for (int h = 0; h < W; h++) {
+    ShardRank& k = pl->r[h];
+    RCHK(on_device(k.device));
+    RCHK(mul_wait_received(pl, h));
+    if (!mp->fused) RCHK(k.p2.run(k.recv, nullptr, k.spec, k.tmp, k.compute));
+  }
+  RCHK(mul_exchange(pl, ish.R, cc, 1, true, [&](int g, int j) {
+    ShardRank& k = pl->r[g];
+    if (!mp->fused)
+      return k.q1.run(k.spec + (u64)j * cc, k.spec + per + (u64)j * cc, k.send2 + (u64)j * ish.R * cc, k.tmp, k.compute, ~(u64)0,
+                      ~(u64)0, 0, (u64)j * cc);
+    const PassDesc& fp = k.p2.pd.passes[0];
+    TileArgs fa, ia;
+    mul_mid_args(k, ish, chunks, j, &fa, &ia);
+    bool found = false;
+    const hipError_t e = launch_mul_mid_dist(fp.logr, fa, ia, fa.tiles, fp.block, fp.lds_bytes, k.compute, &found);
+    if (e != hipSuccess) return hip_fail(e, "launch_mul_mid_dist");
+    return found ? RONK_OK : RONK_ERR_UNSUPPORTED;   // (not reached: the plan checked mul_mid_fusable)
+  }));
+  // inverse phase 2 into the caller's buffers
+  for (int h = 0; h < W; h++) {
+    ShardRank& k = pl->r[h];
+    RCHK(on_device(k.device));
+    RCHK(mul_wait_received(pl, h));
+    RCHK(k.q2.run(k.recv2, nullptr, d_out[h], k.tmp, k.compute));
+    HIPCHK(hipEventRecord(k.done, k.compute));
+    k.used = true;
+  }
+  return RONK_OK;
+}
+
+extern "C" int ronk_sharded_mul_plan_create_p(ronk_sharded_mul_plan** out, uint64_t p, uint64_t g, uint32_t log2n,
+                                              const int* devices, int ndev, int chunks, int exchange, int flags) {
+  const int both = RONK_SHARDED_MUL_UNFUSED | RONK_SHARDED_MUL_FUSED;
+  if (!out || (flags & ~both) || (flags & both) == both) return RONK_ERR_INVALID;
+  *out = nullptr;
+  ronk_sharded_mul_plan* mp = new ronk_sharded_mul_plan();
+  // Default middle: fused only where it measured faster than the composed one (DESIGN.md 6, 8 logical ranks on one GPU, 4 chunks:
+  // 2^24 4.49 against 4.70 ms; 2^22 5.02 against 4.88 ms, and 1.52 against 1.42 ms with 4 ranks).  RONK_SHARDED_MUL_FUSED asks for it
+  // wherever an instantiation matches, RONK_SHARDED_MUL_UNFUSED never.
+  const bool want = (flags & RONK_SHARDED_MUL_FUSED) || (!(flags & RONK_SHARDED_MUL_UNFUSED) && log2n == 24);
+  bool fused = false;
+  int rc = sharded_create(&mp->sp, p, g, log2n, 0, devices, ndev, chunks, exchange, true, want, &fused);
+  if (rc) { delete mp; return rc; }
+  dist_shape_mul((int)log2n, ndev, &mp->ish, true);   // (valid: sharded_create checked it)
+  mp->fused = fused;
+  *out = mp;
+  return RONK_OK;
+}
+extern "C" int ronk_sharded_mul_plan_create(ronk_sharded_mul_plan** out, uint32_t log2n, const int* devices, int ndev, int chunks,
+                                            int exchange, int flags) {
+  return ronk_sharded_mul_plan_create_p(out, RONK_GOLDILOCKS_P, RONK_GOLDILOCKS_G, log2n, devices, ndev, chunks, exchange, flags);
+}
+extern "C" int ronk_sharded_mul_plan_destroy(ronk_sharded_mul_plan* mp) {
+  if (!mp) return RONK_ERR_INVALID;
+  const int rc = ronk_sharded_plan_destroy(mp->sp);
+  delete mp;
+  return rc;
+}
+extern "C" int ronk_sharded_mul_plan_info(const ronk_sharded_mul_plan* mp, uint64_t* rows, uint64_t* cols, uint64_t* per_rank,
+                                          int* chunks, int* fused_middle) {
+  if (!mp) return RONK_ERR_INVALID;
+  if (fused_middle) *fused_middle = mp->fused ? 1 : 0;
+  return ronk_sharded_plan_info(mp->sp, rows, cols, per_rank, chunks);
+}
+extern "C" int ronk_poly_mul_sharded_dev(ronk_sharded_mul_plan* mp, const uint64_t* const* d_a, const uint64_t* const* d_b,
+                                         uint64_t* const* d_out) {
+  if (!mp || !d_a || !d_b || !d_out) return RONK_ERR_INVALID;
+  for (int g = 0; g < mp->sp->ndev; g++)
+    if (!d_a[g] || !d_b[g] || !d_out[g] || d_a[g] == d_out[g] || d_b[g] == d_out[g]) return RONK_ERR_INVALID;
+  std::lock_guard<std::mutex> lk(mp->sp->mu);
+  int prev = 0;
+  HIPCHK(hipGetDevice(&prev));
+  int rc = mul_enqueue(mp, d_a, d_b, d_out);
+  (void)hipSetDevice(prev);
+  return rc;
+}
+extern "C" int ronk_sharded_mul_sync(ronk_sharded_mul_plan* mp) { return mp ? ronk_sharded_sync(mp->sp) : RONK_ERR_INVALID; }
+
+// Host pointers (ronk_poly_mul at a size sharded over the node): zero-pad both operands to n, scatter the column blocks, multiply,
+// gather the first d + d2 - 1 coefficients.
+extern "C" int ronk_poly_mul_sharded(ronk_sharded_mul_plan* mp, const uint64_t* a, size_t d, const uint64_t* b, size_t d2,
+                                     uint64_t* out) {
+  if (!mp || !a || !b || !out || d == 0 || d2 == 0) return RONK_ERR_INVALID;
+  ronk_sharded_plan* pl = mp->sp;
+  const DistShape& sh = pl->sh;
+  const size_t per = (size_t)(sh.n / sh.W), m = d + d2 - 1;
+  if (d > sh.n || d2 > sh.n || m > sh.n) return RONK_ERR_INVALID;
+  std::vector<uint64_t> pa(sh.n, 0), pb(sh.n, 0), full(sh.n);
+  memcpy(pa.data(), a, d * 8);
+  memcpy(pb.data(), b, d2 * 8);
+  int prev = 0;
+  HIPCHK(hipGetDevice(&prev));
+  std::vector<const uint64_t*> da(pl->ndev), db(pl->ndev);
+  std::vector<uint64_t*> dout(pl->ndev);
+  int rc = RONK_OK;
+  {
+    std::lock_guard<std::mutex> lk(pl->mu);
+    for (int g = 0; g < pl->ndev && !rc; g++) {
+      ShardRank& k = pl->r[g];
+      rc = on_device(k.device);
+      hipError_t e = hipSuccess;
+      if (!rc && !k.stage_in) e = hipMalloc((void**)&k.stage_in, 2 * per * 8);   // a and b
+      if (!rc && e == hipSuccess && !k.stage_out) e = hipMalloc((void**)&k.stage_out, per * 8);
+      if (!rc && e == hipSuccess)
+        e = hipMemcpy2DAsync(k.stage_in, sh.Cw * 8, pa.data() + (size_t)g * sh.Cw, sh.C * 8, sh.Cw * 8, sh.R, hipMemcpyHostToDevice, k.compute);
+      if (!rc && e == hipSuccess)
+        e = hipMemcpy2DAsync(k.stage_in + per, sh.Cw * 8, pb.data() + (size_t)g * sh.Cw, sh.C * 8, sh.Cw * 8, sh.R, hipMemcpyHostToDevice, k.compute);
+      if (!rc && e != hipSuccess) rc = hip_fail(e, "scatter");
+      da[g] = k.stage_in; db[g] = k.stage_in + per; dout[g] = k.stage_out;
+    }
+    if (!rc) rc = mul_enqueue(mp, da.data(), db.data(), dout.data());
+    for (int h = 0; h < pl->ndev && !rc; h++) {
+      ShardRank& k = pl->r[h];
+      rc = on_device(k.device);
+      // rank h's [R][C/W] block of the product
+      hipError_t e = hipSuccess;
+      if (!rc) e = hipMemcpy2DAsync(full.data() + (size_t)h * sh.Cw, sh.C * 8, k.stage_out, sh.Cw * 8, sh.Cw * 8, sh.R, hipMemcpyDeviceToHost, k.compute);
+      if (!rc && e == hipSuccess) e = hipStreamSynchronize(k.compute);
+      if (!rc && e != hipSuccess) rc = hip_fail(e, "gather");
+    }
+  }
+  (void)hipSetDevice(prev);
+  if (!rc) memcpy(out, full.data(), m * 8);
   return rc;
 }

@@ -24,4 +24,9 @@ hipError_t launch_mul_mid(int logr, int kindi, const TileArgs& fa, const TileArg
 bool mul_mid_available_mont(int logr, int logc, int kindi);
 hipError_t launch_mul_mid_mont(int logr, int kindi, const TileArgs& fa, const TileArgs& ia, u32 grid, u32 block, size_t lds_bytes,
                                hipStream_t stream, bool* found);
+// the sharded multiply's middle (tile_kernels_dist_mul.hip): fa = forward phase 2 over the operand pair, ia = phase 1 of the
+// swapped-split inverse, both restricted to one inverse column chunk; grid = tiles of ONE operand; Goldilocks or Montgomery (fa.fc)
+bool mul_mid_dist_available(int logr, int logc);
+hipError_t launch_mul_mid_dist(int logr, const TileArgs& fa, const TileArgs& ia, u32 grid, u32 block, size_t lds_bytes,
+                               hipStream_t stream, bool* found);
 }

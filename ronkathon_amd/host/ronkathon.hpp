@@ -426,6 +426,35 @@ class ShardedPlan {
   ronk_sharded_plan* h_ = nullptr;
   size_t n_;
 };
+
+// ronk_sharded_mul_plan: a * b over `devices` (flags: RONK_SHARDED_MUL_UNFUSED / RONK_SHARDED_MUL_FUSED, 0 = the measured default)
+class ShardedMulPlan {
+ public:
+  ShardedMulPlan(uint64_t p, uint64_t g, uint32_t log2n, const std::vector<int>& devices, int chunks = 0,
+                 int exchange = RONK_EXCHANGE_MESH, int flags = 0)
+      : n_((size_t)1 << log2n) {
+    check(ronk_sharded_mul_plan_create_p(&h_, p, g, log2n, devices.data(), (int)devices.size(), chunks, exchange, flags));
+  }
+  ShardedMulPlan(const ShardedMulPlan&) = delete;
+  ShardedMulPlan& operator=(const ShardedMulPlan&) = delete;
+  ~ShardedMulPlan() { if (h_) ronk_sharded_mul_plan_destroy(h_); }
+  bool fused_middle() const {
+    int f = 0;
+    check(ronk_sharded_mul_plan_info(h_, nullptr, nullptr, nullptr, nullptr, &f));
+    return f != 0;
+  }
+  // host coefficient vectors, a.size() + b.size() - 1 <= n: the product
+  std::vector<uint64_t> mul(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) const {
+    if (a.empty() || b.empty() || a.size() + b.size() - 1 > n_) throw Panic(RONK_ERR_INVALID);
+    std::vector<uint64_t> out(a.size() + b.size() - 1);
+    check(ronk_poly_mul_sharded(h_, a.data(), a.size(), b.data(), b.size(), out.data()));
+    return out;
+  }
+
+ private:
+  ronk_sharded_mul_plan* h_ = nullptr;
+  size_t n_;
+};
 }  // namespace device
 
 }  // namespace ronkathon

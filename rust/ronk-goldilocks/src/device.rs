@@ -21,6 +21,7 @@ use std::ptr;
 
 use crate::{
   ffi::{self, check, RonkPlan, RonkPlanOpts, RonkShardedPlan, G, P},
+  ffi_sharded_mul::{self as ffi_mul, RonkShardedMulPlan},
   field::Goldilocks,
 };
 
@@ -514,6 +515,82 @@ impl Drop for ShardedPlan {
   fn drop(&mut self) {
     if !self.raw.is_null() {
       unsafe { ffi::ronk_sharded_plan_destroy(self.raw) };
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- ShardedMulPlan
+/// `ronk_sharded_mul_plan`: `a * b` (the reference's `impl Mul`, src/polynomial/arithmetic.rs:97-119) at a size sharded over
+/// `devices`.  Operands and product are per-rank [R][C/W] column blocks of the zero-padded n-point vectors (the layout of
+/// [`ShardedPlan::transform`]'s input), so products chain without a host round trip.
+pub struct ShardedMulPlan {
+  raw:         *mut RonkShardedMulPlan,
+  pub n:       usize,
+  pub ndev:    usize,
+  pub devices: Vec<i32>,
+}
+unsafe impl Send for ShardedMulPlan {}
+
+impl ShardedMulPlan {
+  /// `ronk_sharded_mul_plan_create_p`; `unfused` forces the composed middle (`SHARDED_MUL_UNFUSED`)
+  pub fn new(p: u64, g: u64, log2n: u32, devices: &[i32], chunks: i32, exchange: Exchange, unfused: bool) -> Self {
+    let mut raw: *mut RonkShardedMulPlan = ptr::null_mut();
+    let ex = match exchange { Exchange::Mesh => ffi::EXCHANGE_MESH, Exchange::Rccl => ffi::EXCHANGE_RCCL };
+    let flags = if unfused { ffi_mul::SHARDED_MUL_UNFUSED } else { 0 };
+    check(unsafe {
+      ffi_mul::ronk_sharded_mul_plan_create_p(&mut raw, p, g, log2n, devices.as_ptr(), devices.len() as c_int, chunks, ex, flags)
+    });
+    Self { raw, n: 1usize << log2n, ndev: devices.len(), devices: devices.to_vec() }
+  }
+
+  /// Goldilocks, the peer-copy mesh, the library's default middle
+  pub fn goldilocks(log2n: u32, devices: &[i32], chunks: i32) -> Self { Self::new(P, G, log2n, devices, chunks, Exchange::Mesh, false) }
+
+  /// (rows R, columns C, elements per rank, column chunks in use, fused middle)
+  pub fn info(&self) -> (u64, u64, u64, i32, bool) {
+    let (mut r, mut c, mut per, mut ch, mut fu) = (0u64, 0u64, 0u64, 0 as c_int, 0 as c_int);
+    check(unsafe { ffi_mul::ronk_sharded_mul_plan_info(self.raw, &mut r, &mut c, &mut per, &mut ch, &mut fu) });
+    (r, c, per, ch, fu != 0)
+  }
+
+  /// uninitialised per-rank blocks, block g on `devices[g]`
+  pub fn alloc_blocks(&self) -> Vec<DevicePoly> {
+    let per = self.info().2 as usize;
+    self.devices.iter().map(|&d| DevicePoly::alloc_on(d, per)).collect()
+  }
+
+  /// host coefficient vectors, `a.len() + b.len() - 1 <= n`: the product (scatter, multiply, gather; synchronous)
+  pub fn mul_host(&self, a: &[Goldilocks], b: &[Goldilocks]) -> Vec<Goldilocks> {
+    assert!(!a.is_empty() && !b.is_empty() && a.len() + b.len() - 1 <= self.n);
+    let mut out = vec![Goldilocks::new(0); a.len() + b.len() - 1];
+    check(unsafe {
+      ffi_mul::ronk_poly_mul_sharded(self.raw, a.as_ptr() as *const u64, a.len(), b.as_ptr() as *const u64, b.len(),
+                                 out.as_mut_ptr() as *mut u64)
+    });
+    out
+  }
+
+  /// device-resident blocks, one per rank on that rank's GPU; asynchronous, see `sync`.  `out` may be an input of a later call.
+  pub fn mul(&self, a: &[&DevicePoly], b: &[&DevicePoly], out: &mut [&mut DevicePoly]) {
+    assert!(a.len() == self.ndev && b.len() == self.ndev && out.len() == self.ndev);
+    let per = self.info().2 as usize;
+    for (g, &d) in self.devices.iter().enumerate() {
+      assert!(a[g].device == d && b[g].device == d && out[g].device == d, "block {g} must live on GPU {d}");
+      assert!(a[g].len == per && b[g].len == per && out[g].len == per);
+    }
+    let pa: Vec<*const u64> = a.iter().map(|p| p.ptr as *const u64).collect();
+    let pb: Vec<*const u64> = b.iter().map(|p| p.ptr as *const u64).collect();
+    let po: Vec<*mut u64> = out.iter().map(|p| p.ptr).collect();
+    check(unsafe { ffi_mul::ronk_poly_mul_sharded_dev(self.raw, pa.as_ptr(), pb.as_ptr(), po.as_ptr()) });
+  }
+
+  pub fn sync(&self) { check(unsafe { ffi_mul::ronk_sharded_mul_sync(self.raw) }); }
+}
+
+impl Drop for ShardedMulPlan {
+  fn drop(&mut self) {
+    if !self.raw.is_null() {
+      unsafe { ffi_mul::ronk_sharded_mul_plan_destroy(self.raw) };
     }
   }
 }

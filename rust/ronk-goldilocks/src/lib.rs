@@ -32,6 +32,7 @@ pub mod bn254;
 pub mod codes;
 pub mod device;
 pub mod ffi;
+pub mod ffi_sharded_mul;
 pub mod field;
 pub mod polynomial;
 pub mod prime64;
