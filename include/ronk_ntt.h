@@ -60,6 +60,7 @@ extern "C" {
 #define RONK_ERR_NOT_ON_CURVE (-11) /* assert!(point.is_on_curve(), "Point is not on curve"), src/curve/mod.rs:79 */
 #define RONK_ERR_NOT_RESIDUE (-13)  /* assert!(self.euler_criterion(), "Element is not a quadratic residue"), prime/mod.rs:179 */
 #define RONK_ERR_RCCL (-12)         /* librccl.so could not be loaded or an RCCL call failed; ronk_last_hip_error() has the text */
+#define RONK_ERR_NOT_CODEWORD (-14) /* the surviving values lie on no polynomial of degree < k (an error, not only erasures) */
 
 const char* ronk_strerror(int code);
 const char* ronk_last_hip_error(void);
@@ -243,6 +244,33 @@ int ronk_rs_decode(uint64_t p, const uint64_t* xs, const uint64_t* ys, size_t k,
  * d_ys receives plan.batch x N y-coordinates (x_i = omega_N^i: ronk_lagrange_nodes).  The zero padding of
  * `Polynomial::from(message)` is implicit (no padded copy) for Goldilocks plans with N >= 2^13. */
 int ronk_rs_encode_batch_dev(ronk_plan* plan, const uint64_t* d_msgs, size_t k, uint64_t* d_ys, void* stream);
+/* prod_i (x - roots[i]): m + 1 coefficients, ascending, the top one ONE (monic); m = 0 gives [1].  Any values (reduced mod p):
+ * repeats and zeros allowed.  A product tree on the device (csrc/roots_kernels.h): leaves of RONK_ROOTS_LEAF factors built
+ * in one workgroup each, then one batched NTT product per level.  Any odd prime while m <= RONK_ROOTS_LEAF; beyond, every
+ * prime with 2^ceil(log2 m) | p - 1 (the tree's top product; m is padded with the root ZERO to RONK_ROOTS_LEAF * 2^t);
+ * otherwise RONK_ERR_UNSUPPORTED.  Workspace 6 x (m padded) words from the event-guarded pool; the level plans are cached by
+ * the library.  Asynchronous on `stream`; not for hipGraph capture (RONK_ERR_UNSUPPORTED while capturing).  Calls of this and
+ * ronk_rs_recover_batch_dev serialise on one library lock while they enqueue. */
+#define RONK_ROOTS_LEAF 64
+int ronk_poly_from_roots(uint64_t p, const uint64_t* roots, size_t m, uint64_t* out);
+int ronk_poly_from_roots_dev(uint64_t p, const uint64_t* d_roots, size_t m, uint64_t* d_out, void* stream);
+/* Reed-Solomon erasure decoding, the inverse of ronk_rs_encode_batch_dev (src/codes/reed_solomon.rs:42-106) on the same plan
+ * (p, g, N = plan n >= 16, B = plan batch).  d_ys: B x N codeword values at x_i = omega_N^i.  d_erased: n_erased DISTINCT
+ * positions (< N), shared by all B rows; their values in d_ys are ignored.  k == 0: RONK_ERR_INVALID; k > N or
+ * n_erased > N - k: RONK_ERR_INDEX.  d_msgs: B x k recovered coefficients.  d_full (may be NULL, may be d_ys): the repaired
+ * B x N codeword.  d_status (required, B ints, written by the call): 0, or RONK_ERR_NOT_CODEWORD for a row whose survivors do
+ * not lie on one polynomial of degree < k (its d_msgs / d_full rows are then meaningless); RONK_ERR_ZERO_INVERSE (repeated
+ * position -- the reference's coincident-node panic) or RONK_ERR_INDEX (position >= N) in EVERY entry for a malformed list.
+ * O(N log N) per row: Z_E = prod_{i in E} (x - omega^i) by the product tree (fields as for ronk_poly_from_roots), then three
+ * size-N transforms on the plan (four with d_full) and element-wise passes; the erased-set work is shared by the batch.
+ * Needs a coset s * <omega_N> (s = g unless g^N = 1): N = p - 1 is RONK_ERR_UNSUPPORTED.  Peak workspace (words):
+ * 2N + max(B N, 6 Mp) + N / 64 + 8, Mp = n_erased padded to RONK_ROOTS_LEAF * 2^t.  Asynchronous; not for capture. */
+int ronk_rs_recover_batch_dev(ronk_plan* plan, size_t k, const uint64_t* d_erased, size_t n_erased, const uint64_t* d_ys,
+                              uint64_t* d_msgs, uint64_t* d_full, int* d_status, void* stream);
+/* one codeword, host pointers (a plan of batch 1 per call); returns RONK_ERR_NOT_CODEWORD for an inconsistent codeword, and
+ * the list errors as above */
+int ronk_rs_recover(uint64_t p, uint64_t g, size_t n, size_t k, const uint64_t* erased, size_t n_erased, const uint64_t* ys,
+                    uint64_t* msg, uint64_t* full);
 /* Low-degree extension: a batch of polynomials given by their values on {omega_K^i} (plan_k: n = K) -> their values on
  * coset_shift * {omega_N^i} (plan_n: n = N >= K, same batch and modulus).  = Message::encode::<N> of lagrange_poly.ifft()
  * (src/polynomial/mod.rs:430-453, src/codes/reed_solomon.rs:42-52), the coefficients multiplied by coset_shift^i first when

@@ -29,6 +29,8 @@ ERR_NO_GENERATOR, ERR_INDEX, ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_NO_DEVIC
 ERR_NOT_ON_CURVE = -11
 ERR_RCCL = -12
 ERR_NOT_RESIDUE = -13
+ERR_NOT_CODEWORD = -14
+ROOTS_LEAF = 64   # RONK_ROOTS_LEAF: factors per leaf of the product tree (ronk_poly_from_roots)
 EXCHANGE_MESH, EXCHANGE_RCCL = 0, 1
 
 
@@ -101,6 +103,10 @@ _SIG = {
     "ronk_rs_encode": (_int, [_u64, _u64, _vp, _sz, _sz, _vp, _vp]),
     "ronk_rs_decode": (_int, [_u64, _vp, _vp, _sz, _vp]),
     "ronk_rs_encode_batch_dev": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "ronk_poly_from_roots": (_int, [_u64, _vp, _sz, _vp]),
+    "ronk_poly_from_roots_dev": (_int, [_u64, _vp, _sz, _vp, _vp]),
+    "ronk_rs_recover_batch_dev": (_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ronk_rs_recover": (_int, [_u64, _u64, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
     "ronk_lde_batch_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "ronk_curve_msm": (_int, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "ronk_msm_bn254": (_int, [_vp, _vp, _sz, _vp]),
@@ -261,6 +267,12 @@ class Plan:
     def rs_encode_batch_dev(self, d_msgs, k, d_ys, stream=0):
         """batched Message::encode::<N> (codes/reed_solomon.rs:42-52): [batch][k] messages -> [batch][n] y-coordinates"""
         check(lib.ronk_rs_encode_batch_dev(self.h, d_msgs, k, d_ys, stream))
+
+    def rs_recover_batch_dev(self, k, d_erased, n_erased, d_ys, d_msgs, d_full, d_status, stream=0):
+        """erasure recovery, the inverse of rs_encode_batch_dev (ronk_rs_recover_batch_dev): [batch][n] codewords with the same
+        n_erased positions lost -> [batch][k] messages (d_full, may be None: the repaired codewords); d_status receives one int
+        per row (0, ERR_NOT_CODEWORD, or the list's ERR_ZERO_INVERSE / ERR_INDEX in every entry)"""
+        check(lib.ronk_rs_recover_batch_dev(self.h, k, d_erased, n_erased, d_ys, d_msgs, d_full, d_status, stream))
 
     def time_passes(self, d_in, d_out, inverse=False, iters=20, stream=0):
         np_ = self.num_passes()

@@ -41,6 +41,33 @@ class Message:
         msg.field, msg.data = field, out
         return msg
 
+    @classmethod
+    def recover(cls, field, N, erased, ys, K):
+        """Erasure decoding of a codeword of N points x_i = omega_N^i (the inverse of `encode(N)`): the values at the
+        positions in `erased` are lost (ignored), the message is rebuilt from all the others in O(N log N)
+        (ronk_rs_recover).  Returns (message, repaired codeword); a codeword whose survivors lie on no polynomial of degree
+        < K raises RonkPanic(ERR_NOT_CODEWORD)."""
+        ys = L.arr([int(v) % field.ORDER for v in ys])
+        if ys.size != N:
+            raise L.RonkPanic(L.ERR_INDEX, "a codeword has N values")
+        er = L.arr([int(v) for v in erased])
+        out = np.empty(K, dtype=np.uint64)
+        full = np.empty(N, dtype=np.uint64)
+        L.check(L.lib.ronk_rs_recover(field.ORDER, field._G, N, K, L.ptr(er) if er.size else None, er.size, L.ptr(ys),
+                                      L.ptr(out), L.ptr(full)))
+        msg = cls.__new__(cls)
+        msg.field, msg.data = field, out
+        return msg, full
+
+
+def poly_from_roots(field, roots):
+    """prod_i (x - roots[i]) as a Polynomial (monic, m + 1 coefficients): the product tree on the device
+    (ronk_poly_from_roots) -- the coefficients of Message::decode's x_combinations (codes/reed_solomon.rs:54-106)."""
+    r = L.arr([int(v) % field.ORDER for v in roots])
+    out = np.empty(r.size + 1, dtype=np.uint64)
+    L.check(L.lib.ronk_poly_from_roots(field.ORDER, L.ptr(r) if r.size else None, r.size, L.ptr(out)))
+    return Polynomial.new(field, out)
+
 
 def kzg_open_quotient(field, coeffs, eval_point):
     """`kzg::open`'s polynomial step (kzg/setup.rs:63-78): Polynomial::new(coeffs).div([-z, 1])."""

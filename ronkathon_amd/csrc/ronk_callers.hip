@@ -178,6 +178,16 @@ struct WsLease {
   }
   void lb_commit() { slot->lb_calls++; }
 };
+// The pool for other translation units (runtime.h): one lease, released (event behind the work queued on `s`) by ws_lease_release
+int ws_lease_acquire(size_t bytes, hipStream_t s, void** lease, u64** ptr) {
+  WsLease* w = new WsLease();
+  const int rc = w->acquire(bytes, s);
+  if (rc != RONK_OK) { delete w; return rc; }
+  *lease = w;
+  *ptr = w->u();
+  return RONK_OK;
+}
+void ws_lease_release(void* lease) { delete (WsLease*)lease; }
 // Releases every idle pool slot and every finished one-off buffer (include/ronk_ntt.h).  Waits for the work behind them
 // (events; a slot released in single-stream mode has none: its device is synchronised).
 extern "C" int ronk_trim_workspace(void) {

@@ -34,6 +34,7 @@ extern "C" const char* ronk_strerror(int code) {
     case RONK_ERR_NOT_ON_CURVE: return "Point is not on curve";
     case RONK_ERR_RCCL: return "RCCL error";
     case RONK_ERR_NOT_RESIDUE: return "Element is not a quadratic residue";
+    case RONK_ERR_NOT_CODEWORD: return "the surviving values lie on no polynomial of degree < k";
     default: return "unknown error";
   }
 }

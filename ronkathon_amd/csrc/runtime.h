@@ -35,6 +35,11 @@ int need_device();                              // RONK_OK or RONK_ERR_NO_DEVICE
     if (rc_ != RONK_OK) return rc_; \
   } while (0)
 
+// ---- the event-guarded workspace pool (ronk_callers.hip): a lease of at least `bytes`, asynchronous on `s`; release it once
+//      the work that uses it has been queued
+int ws_lease_acquire(size_t bytes, hipStream_t s, void** lease, u64** ptr);
+void ws_lease_release(void* lease);
+
 // ---- host integer logic
 typedef unsigned __int128 u128;
 static inline u64 h_mulmod(u64 a, u64 b, u64 p) { return (u64)(((u128)a * b) % p); }

@@ -240,7 +240,26 @@ struct Message {                                                                
     check(ronk_rs_decode(F::ORDER, xs.data(), ys.data(), K, reinterpret_cast<uint64_t*>(m.data.data())));
     return m;
   }
+  // erasure decoding of encode::<N>'s y-coordinates from ALL survivors, O(N log N) (ronk_rs_recover): the values at `erased`
+  // are ignored; returns the message, `full` receives the repaired y-coordinates.  Throws RONK_ERR_NOT_CODEWORD for survivors
+  // on no polynomial of degree < K.
+  template <size_t N> static Message recover(const std::array<F, N>& ys, const std::vector<uint64_t>& erased, std::array<F, N>* full = nullptr) {
+    static_assert(N >= K, "Code size must be greater than or equal to K");
+    Message m;
+    check(ronk_rs_recover(F::ORDER, F::PRIMITIVE_ELEMENT().value, N, K, erased.empty() ? nullptr : erased.data(), erased.size(),
+                          reinterpret_cast<const uint64_t*>(ys.data()), reinterpret_cast<uint64_t*>(m.data.data()),
+                          full ? reinterpret_cast<uint64_t*>(full->data()) : nullptr));
+    return m;
+  }
 };
+
+// prod_i (x - roots[i]), monic, roots.size() + 1 coefficients (the product tree, ronk_poly_from_roots)
+template <class F> std::vector<F> poly_from_roots(const std::vector<F>& roots) {
+  std::vector<F> out(roots.size() + 1);
+  check(ronk_poly_from_roots(F::ORDER, roots.empty() ? nullptr : reinterpret_cast<const uint64_t*>(roots.data()), roots.size(),
+                             reinterpret_cast<uint64_t*>(out.data())));
+  return out;
+}
 
 // ---- KZG commit / open (src/kzg/setup.rs:45-78) over AffinePoint<PlutoExtendedCurve> (src/curve/mod.rs:66-73) --------
 struct AffinePoint {                       // Point(x, y) with x = x0 + x1 t, y = y0 + y1 t in GF(101^2), or Infinity
@@ -386,6 +405,20 @@ class Plan {
     check(ronk_ntt_forward_many_dev(h_, in.data(), out.data(), in.size(), nullptr));
   }
   // host vectors through the plan (a batch is pipelined over its polynomials: upload | transform | download)
+  // erasure decoding of `batch` codewords (encode layout, batch x n) that lost the same positions (ronk_rs_recover_batch_dev):
+  // msgs receives batch x k coefficients; returns one status per row (0 or RONK_ERR_NOT_CODEWORD; a malformed list throws)
+  std::vector<int> recover_batch(size_t k, const std::vector<uint64_t>& erased, const DevicePoly& ys, DevicePoly& msgs) const {
+    need(ys);
+    if (msgs.size() != k * batch_) throw Panic(RONK_ERR_INVALID);
+    DevicePoly er(erased.empty() ? std::vector<uint64_t>{0} : erased), status((batch_ + 1) / 2);
+    check(ronk_rs_recover_batch_dev(h_, k, er.data(), erased.size(), ys.data(), msgs.data(), nullptr, reinterpret_cast<int*>(status.data()),
+                                    nullptr));
+    const std::vector<uint64_t> w = status.to_host();
+    std::vector<int> st(batch_);
+    for (size_t b = 0; b < batch_; b++) st[b] = (int)(uint32_t)(w[b / 2] >> (32 * (b % 2)));
+    for (int e : st) if (e == RONK_ERR_ZERO_INVERSE || e == RONK_ERR_INDEX) throw Panic(e);
+    return st;
+  }
   std::vector<uint64_t> forward_host(const std::vector<uint64_t>& x) const {
     if (x.size() != n() * batch_) throw Panic(RONK_ERR_INVALID);
     std::vector<uint64_t> y(x.size());

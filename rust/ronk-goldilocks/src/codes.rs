@@ -11,6 +11,7 @@
 //! * [`encode_batch`]        = `encode::<N>` of `plan.batch` messages at once, y-coordinates only       -> `ronk_rs_encode_batch_dev`
 //! * [`lde`]                 = `lagrange.ifft()` (mod.rs:430-453) then `encode::<N>` on a coset         -> `ronk_lde_batch_dev`
 //! * [`decode_dev`]          = `decode` on device-resident coordinates                                -> `ronk_rs_decode_dev`
+//! * `Message::recover::<N>` / [`recover_batch`] = erasure decoding from ALL survivors, O(N log N)   -> `ronk_rs_recover(_batch_dev)`
 use core::ffi::{c_int, c_void};
 use std::ptr;
 
@@ -63,6 +64,45 @@ impl<const K: usize> Message<K> {
     check(unsafe { ffi::ronk_rs_decode(P, xs.as_ptr(), ys.as_ptr(), K, out.as_mut_ptr()) });
     Message { data: core::array::from_fn(|i| Goldilocks(out[i])) }
   }
+
+  /// Erasure decoding of `encode::<N>`'s codeword: the y-coordinates at the positions in `erased` are lost (their values are
+  /// ignored), the message is rebuilt from all the others in O(N log N) (`ronk_rs_recover`).  Returns the message and the repaired
+  /// y-coordinates.  Panics: a repeated position (coincident nodes), a position >= N, more than N - K erasures, or survivors
+  /// that lie on no polynomial of degree < K (`RONK_ERR_NOT_CODEWORD`).
+  pub fn recover<const N: usize>(ys: &[Goldilocks; N], erased: &[usize]) -> (Self, Vec<Goldilocks>) {
+    assert!(N >= K, "Code size must be greater than or equal to K");
+    let er: Vec<u64> = erased.iter().map(|&i| i as u64).collect();
+    let (mut out, mut full) = (vec![0u64; K], vec![0u64; N]);
+    check(unsafe {
+      ffi::ronk_rs_recover(P, G, N, K, if er.is_empty() { ptr::null() } else { er.as_ptr() }, er.len(), ys.as_ptr() as *const u64,
+                           out.as_mut_ptr(), full.as_mut_ptr())
+    });
+    (Message { data: core::array::from_fn(|i| Goldilocks(out[i])) }, full.into_iter().map(Goldilocks).collect())
+  }
+}
+
+/// Erasure decoding of `plan.batch` codewords (`encode_batch`'s output layout, batch x N) that lost the same positions:
+/// returns the batch x k messages and one status per row (0, or -14 = `RONK_ERR_NOT_CODEWORD` for a row whose survivors lie on
+/// no polynomial of degree < k).  A malformed erasure list (repeated position, position >= N) panics.
+pub fn recover_batch(plan: &Plan, k: usize, erased: &[usize], ys: &DevicePoly) -> (DevicePoly, Vec<i32>) {
+  assert!(k >= 1 && k <= plan.n(), "Code size must be greater than or equal to K");
+  assert!(ys.len() == plan.batch * plan.n());
+  plan.same_device(ys);
+  let _g = OnDevice::new(plan.device());
+  let er: Vec<Goldilocks> = erased.iter().map(|&i| Goldilocks(i as u64)).collect();
+  let d_er = DevicePoly::from_host_on(plan.device(), &er);
+  let out = DevicePoly::alloc_on(plan.device(), plan.batch * k);
+  let status = DevicePoly::alloc_on(plan.device(), (plan.batch + 1) / 2);   // B ints in 8-byte words
+  check(unsafe {
+    ffi::ronk_rs_recover_batch_dev(plan.raw(), k, d_er.as_ptr(), erased.len(), ys.as_ptr(), out.as_mut_ptr(), ptr::null_mut(),
+                                   status.as_mut_ptr() as *mut c_int, ptr::null_mut())
+  });
+  let words = status.to_host();
+  let st: Vec<i32> = (0..plan.batch).map(|b| (words[b / 2].0 >> (32 * (b % 2))) as u32 as i32).collect();
+  if let Some(&e) = st.iter().find(|&&e| e == -2 || e == -6) {
+    check(e);   // the reference's coincident-node panic / an index out of bounds
+  }
+  (out, st)
 }
 
 /// `encode::<N>` of `plan.batch` messages in one launch pair: `msgs` holds `batch` compact messages of `k` coefficients,

@@ -156,6 +156,17 @@ extern "C" {
   pub fn ronk_rs_decode_dev(
     p: u64, d_xs: *const u64, d_ys: *const u64, k: usize, d_out: *mut u64, d_status: *mut c_int, stream: *mut c_void,
   ) -> c_int;
+  /// prod_i (x - roots[i]): m + 1 coefficients, monic (the product tree, include/ronk_ntt.h)
+  pub fn ronk_poly_from_roots(p: u64, roots: *const u64, m: usize, out: *mut u64) -> c_int;
+  pub fn ronk_poly_from_roots_dev(p: u64, d_roots: *const u64, m: usize, d_out: *mut u64, stream: *mut c_void) -> c_int;
+  /// erasure decoding, the inverse of `ronk_rs_encode_batch_dev` on the same plan; `d_status`: one int per row
+  pub fn ronk_rs_recover_batch_dev(
+    plan: *mut RonkPlan, k: usize, d_erased: *const u64, n_erased: usize, d_ys: *const u64, d_msgs: *mut u64, d_full: *mut u64,
+    d_status: *mut c_int, stream: *mut c_void,
+  ) -> c_int;
+  pub fn ronk_rs_recover(
+    p: u64, g: u64, n: usize, k: usize, erased: *const u64, n_erased: usize, ys: *const u64, msg: *mut u64, full: *mut u64,
+  ) -> c_int;
   pub fn ronk_vec_add_dev(p: u64, a: *const u64, b: *const u64, out: *mut u64, n: usize, stream: *mut c_void) -> c_int;
   pub fn ronk_vec_sub_dev(p: u64, a: *const u64, b: *const u64, out: *mut u64, n: usize, stream: *mut c_void) -> c_int;
   pub fn ronk_vec_mul_dev(p: u64, a: *const u64, b: *const u64, out: *mut u64, n: usize, stream: *mut c_void) -> c_int;
