@@ -79,6 +79,13 @@ inline bool mul_mid_matches(const TileArgs& fa, const TileArgs& ia, int logr, in
          tile_cfg_matches(ia, logr, logc, kindi);
 }
 
+// the instantiated (rows, tile width, inverse twiddle form) combinations (tile_kernels_mul.hip / tile_kernels_mont_mul.hip).
+// Goldilocks, 4- and 8-column tiles: 2^11-row passes = NTT size 2^22; 2^10-row passes = NTT size 2^21 (pair plan 2^11 x 2^10,
+// inverse split the other way round) and 2^20 (instantiated, but conv_dev keeps four launches there: measured slower fused).
+// Montgomery: the same shapes with 4-column tiles, 2^11-row passes (NTT sizes 2^22, 2^23) and 2^10-row passes (2^21).
+#define RONK_MUL_MID_TABLE(X) X(11, 2, 1) X(11, 2, 3) X(11, 3, 1) X(11, 3, 3) X(10, 2, 1) X(10, 2, 3) X(10, 3, 1) X(10, 3, 3)
+#define RONK_MUL_MID_TABLE_MONT(X) X(11, 2, 1) X(11, 2, 3) X(10, 2, 1) X(10, 2, 3)
+
 // The sharded multiply's middle (ronk_dist.hip): fa = forward phase 2 over the operand pair (receive buffer, rows in blocks of
 // 2^js_log, batch of two), ia = phase 1 of the swapped-split inverse (KIND 4: global twiddle with the rank's column offset,
 // n^-1 folded in).  One tile of each: the same C local k1 columns, every k2.  The forward side must be a KIND 2 row pass: its

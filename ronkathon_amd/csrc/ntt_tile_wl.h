@@ -56,7 +56,9 @@ inline bool tile_wl_matches(const TileArgs& a, int logr, int kind) {
     b.tf_sc = 1; b.tf_sk = (u32)a.ncols;   // what tile_cfg_matches knows as the matrix of a column pass
     return a.logc == (u32)WL_LOGC && a.tf_sb2 == 0 && tile_cfg_matches(b, logr, WL_LOGC, 3, 0);
   }
-  return tile_cfg_matches(a, logr, WL_LOGC, kind, 0);
+  // the row pass needs blocked rows (tile_body_wl_row steps by (16 * RL) >> js_log blocks): a flat-row pass (js_log = 31, the
+  // last pass of a three-pass plan) is no WL pass
+  return tile_cfg_matches(a, logr, WL_LOGC, kind, 0) && (kind != 2 || a.js_log < 31);
 }
 
 // One LDS cell of the image: 8-byte cells (FULL) or the low / high word of a coefficient in a 4-byte cell

@@ -1,5 +1,6 @@
 // ronk_msm.hip -- C ABI of libronk_ntt.so, part 5: kzg::commit on a production-size curve -- the bucket-method MSM over
 // BN254 G1 (reference fold: src/kzg/setup.rs:48-60).  Kernels: msm_kernels.h; arithmetic: bn254.h.
+#include "hip_launch.h"
 #include "runtime.h"
 #include "msm_kernels.h"
 #include "fr_scan_kernels.h"
@@ -121,20 +122,14 @@ int msm_run(const u64* d_points, const u64* d_scalars, size_t n, u64 out[8], hip
   hipLaunchKernelGGL(msm_prepare_kernel, dim3(gn), dim3(256), 0, s, d_points, sh.n, (Affine*)wk.pts.p, (int*)wk.status.p);
   // counting sort of the entries by (window, bucket)
   {
-    static bool attr_done[64] = {};
     const size_t lds = (size_t)sh.NB * 4;
-    if (lds > 48 * 1024 && !attr_done[dev]) {
-      HIPCHK(hipFuncSetAttribute((const void*)msm_sort_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void*)msm_sort_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_done[dev] = true;
-    }
     const size_t m = (size_t)keys * wk.chunks;
     hipLaunchKernelGGL(msm_carries_kernel, dim3(gn), dim3(256), 0, s, d_scalars, sh, (u64*)wk.carries.p);
-    hipLaunchKernelGGL((msm_sort_kernel<false>), dim3(wk.chunks, sh.W), dim3(MSM_SORT_WG), lds, s, d_scalars,
-                       (const u64*)wk.carries.p, sh, wk.chunk_size, wk.chunks, (u32*)wk.hist.p, (const u32*)nullptr, (u32*)nullptr);
+    HIPCHK(launch_dyn<msm_sort_kernel<false>>(dim3(wk.chunks, sh.W), dim3(MSM_SORT_WG), lds, s, d_scalars, (const u64*)wk.carries.p, sh,
+                                              wk.chunk_size, wk.chunks, (u32*)wk.hist.p, (const u32*)nullptr, (u32*)nullptr));
     msm_scan(wk, (const u32*)wk.hist.p, m, (u32*)wk.pos.p, s);
-    hipLaunchKernelGGL((msm_sort_kernel<true>), dim3(wk.chunks, sh.W), dim3(MSM_SORT_WG), lds, s, d_scalars,
-                       (const u64*)wk.carries.p, sh, wk.chunk_size, wk.chunks, (u32*)nullptr, (const u32*)wk.pos.p, (u32*)wk.entries.p);
+    HIPCHK(launch_dyn<msm_sort_kernel<true>>(dim3(wk.chunks, sh.W), dim3(MSM_SORT_WG), lds, s, d_scalars, (const u64*)wk.carries.p, sh,
+                                             wk.chunk_size, wk.chunks, (u32*)nullptr, (const u32*)wk.pos.p, (u32*)wk.entries.p));
     hipLaunchKernelGGL(msm_offsets_kernel, dim3((keys + 256) / 256), dim3(256), 0, s, (const u32*)wk.pos.p, keys, wk.chunks, wk.ch,
                        (u32*)wk.offsets.p, (u32*)wk.ntasks.p);
   }

@@ -6,6 +6,7 @@
 #include "runtime.h"
 #include "ntt_mul.h"
 #include "ntt_aux_kernels.h"
+#include "tile_select.h"
 
 // ------------------------------------------------------------------------------------- plans
 
@@ -144,8 +145,7 @@ extern "C" int ronk_plan_create_opts(ronk_plan** out, uint64_t p, uint64_t g, ui
     // instruction lose against 32-byte pieces of lines that four neighbouring tiles pull through the same L2 at the same time.
     // RONK_TWF_T = 0 (default) never, 1 the automatic two-lane plans, 2 every plan with such a pass.
     static const int twf_t_mode = [] { const char* e = getenv("RONK_TWF_T"); return e ? atoi(e) : 0; }();
-    bool wl_half_ = false;
-    const bool twf_t = tile_wl_wanted(3, &wl_half_) && (twf_t_mode == 2 || (twf_t_mode == 1 && in_flight == 2 && tile_log2_columns < 0 && max_logc == 2));
+    const bool twf_t = tile_wl_wanted(tile_env(), 3) && (twf_t_mode == 2 || (twf_t_mode == 1 && in_flight == 2 && tile_log2_columns < 0 && max_logc == 2));
     rc = pl->fwd.compile(build_plan((int)log2n, batch, false, max_logc, twf_max_log, three_from, auto_tiles, split_ka, hf, twf_t));
     if (!rc) rc = pl->inv.compile(build_plan((int)log2n, batch, true, max_logc, twf_max_log, three_from, auto_tiles, split_ka, hf, twf_t));
     for (auto& ps : pl->fwd.pd.passes)  // grid must fit the launch API
@@ -863,21 +863,14 @@ static int conv_dev(u64 p, u64 g, int k, const u64* d_a, size_t d, const u64* d_
         //  pl2->d_tmp and plf->d_tmp are used directly, without stream_mu / scratch_acquire / scratch_release: both plans are
         //  private to this cache entry, and every use of the entry is serialised by g_cache_mu (held here) + e->done -- that
         //  pair is the ONLY guard of these two scratch buffers.)
-        const bool mont = pl->mont_tiled;
-        if (mul_mid_matches(fa, ia, fp.logr, (int)fa.logc, kindi) &&
-            (mont ? mul_mid_available_mont(fp.logr, (int)fa.logc, kindi) : mul_mid_available(fp.logr, (int)fa.logc, kindi))) {
+        if (mul_mid_matches(fa, ia, fp.logr, (int)fa.logc, kindi) && mul_mid_available(fp.logr, (int)fa.logc, kindi, fa.fc.p != 0)) {
           HIPCHK(entry_wait(s, e->done));
           RCHK(F.launch(0, d_a, nullptr, nullptr, e->pl2->d_tmp, s, (u64)d, ~(u64)0, stride, 0, 0, 0, (u64)d2));
-          bool found = false;
-          hipError_t he = mont ? launch_mul_mid_mont(fp.logr, kindi, fa, ia, fa.tiles, fp.block, fp.lds_bytes, s, &found)
-                               : launch_mul_mid(fp.logr, kindi, fa, ia, fa.tiles, fp.block, fp.lds_bytes, s, &found);
+          hipError_t he = launch_mul_mid(fp.logr, kindi, fa, ia, fa.tiles, fp.block, fp.lds_bytes, s);
           if (he != hipSuccess) return hip_fail(he, "launch_mul_mid");
-          if (found) {
-            RCHK(I.launch(1, nullptr, nullptr, d_out, e->plf->d_tmp, s, ~(u64)0, (u64)m));
-            HIPCHK(entry_record(e->done, s));
-            return RONK_OK;
-          }
-          // (not reached: mul_mid_available said yes)
+          RCHK(I.launch(1, nullptr, nullptr, d_out, e->plf->d_tmp, s, ~(u64)0, (u64)m));
+          HIPCHK(entry_record(e->done, s));
+          return RONK_OK;
         }
       }
     }

@@ -1,6 +1,6 @@
 // tile_cfg_table.h -- the (LOGR, LOGC, KIND) combinations that have a compile-time-specialised tile kernel (TileCfg,
-// ntt_tile.h).  One list, used by the launcher (tile_kernels_cfg.hip) and by the host emulator (tests/emu) so that the
-// very same instantiations are checked against the oracle on the CPU.
+// ntt_tile.h).  One list, used by the selection rule (tile_select.h), the launchers (tile_kernels_cfg.hip and its siblings) and
+// the host emulator (tests/emu), so that the very same instantiations are checked against the oracle on the CPU.
 //   KIND 1 (column pass, two-level inter-pass twiddle)   2^19 .. 2^22; first pass of the three-pass plans 2^23 .. 2^28
 //   KIND 3 (column pass, full twiddle matrix)            2^16 .. 2^18 (default), 2^21 / 2^22 when the plan asks for it; middle
 //                                                        pass of the three-pass plans

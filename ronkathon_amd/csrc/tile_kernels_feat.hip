@@ -7,18 +7,15 @@
 
 namespace ronk {
 
-#define RONK_FEAT_CASE(LR, LC, KD, FT)                                                                    \
-  if (logr == LR && (int)a.logc == LC && kind == KD && feat == FT) {                                      \
-    *found = true;                                                                                        \
-    return inverse ? launch_one_feat<LR, true, LC, KD, FT>(a, grid, block, lds, s)                        \
-                   : launch_one_feat<LR, false, LC, KD, FT>(a, grid, block, lds, s);                      \
-  }
-
 hipError_t launch_tile_cfg_feat(int logr, bool inverse, int kind, int feat, const TileArgs& a, u32 grid, u32 block, size_t lds,
-                                hipStream_t s, bool* found) {
+                                hipStream_t s) {
+#define RONK_FEAT_CASE(LR, LC, KD, FT)                                                                    \
+  if (logr == LR && (int)a.logc == LC && kind == KD && feat == FT)                                        \
+    return inverse ? launch_dyn<ntt_tile_kernel_feat<LR, true, LC, KD, FT>>(grid, block, lds, s, a)       \
+                   : launch_dyn<ntt_tile_kernel_feat<LR, false, LC, KD, FT>>(grid, block, lds, s, a);
   RONK_CFG_TABLE_FEAT(RONK_FEAT_CASE)
-  *found = false;
-  return hipSuccess;
+#undef RONK_FEAT_CASE
+  return hipErrorInvalidValue;
 }
 
 }  // namespace ronk

@@ -13,14 +13,14 @@
 #include <string.h>
 #include <ucontext.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../oracle/ronk_oracle.h"
 #include "../../ronkathon_amd/csrc/plan.h"
 #include "../../ronkathon_amd/csrc/ntt_small.h"
 #include "../../ronkathon_amd/csrc/ntt_mul.h"
-#include "../../ronkathon_amd/csrc/tile_cfg_table.h"
-#include "../../ronkathon_amd/csrc/ntt_tile_wl.h"
+#include "../../ronkathon_amd/csrc/tile_select.h"
 
 using namespace ronk;
 
@@ -31,7 +31,7 @@ static std::vector<char> g_done;
 static int g_cur;
 
 struct FiberArgs {
-  const TileArgs* a; u64* lds; u32 bid; int logr; bool inv; bool small;
+  const TileArgs* a; u64* lds; u32 bid; int logr; bool inv; bool small; TileChoice choice;
 };
 static FiberArgs g_fa;
 
@@ -44,140 +44,86 @@ static bool g_mont = false;
 static HostField g_hf;
 static u64 rnd_elem(u64& s);
 
-template <int LOGR, bool INV, class FLD>
-static void run_body(u32 tid) { tile_body<LOGR, INV, 0, TileCfg<-1, 0>, FLD>(*g_fa.a, g_fa.lds, tid, g_fa.bid, fiber_barrier); }
-
-// the compile-time-specialised instantiations the library launches for recognised pass shapes (tile_kernels.hip):
-// same selection rule, same table
-static int g_cfg_used = 0;
+// the body the library launches for this pass (tile_select.h: the same rule, the same tables)
 template <bool INV, class FLD>
-static bool dispatch_cfg(int logr, u32 tid) {
+static bool run_choice(int logr, u32 tid) {
   const TileArgs& a = *g_fa.a;
-  static const bool half = getenv("RONK_HALF_LDS") && atoi(getenv("RONK_HALF_LDS")) == 1;   // TileCfg::HALF instantiations
-  // the wave-local bodies of the 2^11-row x 4-column passes (ntt_tile_wl.h), selected like the library does: RONK_WL = 0 off, 1
-  // (default) both passes, 2 column pass only, 3 row pass only; RONK_WL_HALF=1 the half-image form (Goldilocks)
-  {
-    static const int wl = getenv("RONK_WL") ? atoi(getenv("RONK_WL")) : 1;
-    static const bool wl_half = getenv("RONK_WL_HALF") && atoi(getenv("RONK_WL_HALF")) != 0;
-    static const bool r4_first = getenv("RONK_R4MID") && atoi(getenv("RONK_R4MID")) != 0;   // the opt-in below wins at 2^10 rows
-    if (wl && wl_logr_ok(logr) && (int)a.logc == WL_LOGC && !(r4_first && logr == 10)) {
-      for (int kind : {1, 2, 3}) {
-        if (!tile_wl_matches(a, logr, kind)) continue;
-        if (kind == 2 ? wl == 2 : wl == 3) continue;
-        u32* l32 = reinterpret_cast<u32*>(g_fa.lds);
+  const TileChoice c = g_fa.choice;
+  const int logc = (int)a.logc;
+  switch (c.form) {
+    case TileForm::WL_FULL:
+    case TileForm::WL_HALF: {
+      u32* l32 = reinterpret_cast<u32*>(g_fa.lds);
 #define EMU_WL_RUN(LR, FULLIMG)                                                                                                  \
   do {                                                                                                                           \
-    if (kind == 1) tile_body_wl_col<LR, INV, 1, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);              \
-    else if (kind == 3) tile_body_wl_col<LR, INV, 3, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);         \
+    if (c.kind == 1) tile_body_wl_col<LR, INV, 1, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);            \
+    else if (c.kind == 3) tile_body_wl_col<LR, INV, 3, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);       \
     else tile_body_wl_row<LR, INV, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);                           \
   } while (0)
-        if (wl_half && !FLD::MONT && logr == 11) EMU_WL_RUN(11, false);
-        else if (logr == 10) EMU_WL_RUN(10, true);
-        else if (logr == 11) EMU_WL_RUN(11, true);
-        else EMU_WL_RUN(12, true);
+      if (c.form == TileForm::WL_HALF) EMU_WL_RUN(11, false);
+      else if (logr == 10) EMU_WL_RUN(10, true);
+      else if (logr == 11) EMU_WL_RUN(11, true);
+      else EMU_WL_RUN(12, true);
 #undef EMU_WL_RUN
-        g_cfg_used = 30 + kind;
-        return true;
-      }
+      return true;
     }
-  }
-  if constexpr (FLD::MONT) {   // the shapes the library instantiates for Montgomery primes (tile_kernels_mont.hip): the plain table
-    if (const int feat = tile_features(a)) {   // ... and the feature shapes in the direction they occur in (tile_kernels_mont_feat.hip)
-#define EMU_MONT_FEAT_CASE(LR, LC, KD, FT)                                                       \
-  if (logr == LR && (int)a.logc == LC && feat == FT && INV == (FT != 1) && tile_cfg_matches(a, LR, LC, KD, FT)) { \
-    tile_body<LR, (FT != 1), 0, TileCfg<LC, KD, false, false, FT>, FLD>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); \
-    g_cfg_used = KD + 100 * FT;                                                                  \
-    return true;                                                                                 \
-  }
-      RONK_CFG_TABLE_FEAT(EMU_MONT_FEAT_CASE)
-#undef EMU_MONT_FEAT_CASE
-      return false;
+    case TileForm::FEAT:   // (Montgomery: instantiated in the direction the feature occurs in)
+#define EMU_FEAT_CASE(LR, LC, KD, FT)                                                                                   \
+  if constexpr (!FLD::MONT || INV == (FT != 1))                                                                         \
+    if (logr == LR && logc == LC && c.kind == KD && c.feat == FT) {                                                     \
+      tile_body<LR, INV, 0, TileCfg<LC, KD, false, false, FT>, FLD>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier);        \
+      return true;                                                                                                      \
     }
-#define EMU_MONT_CASE(LR, LC, KD)                                                                \
-  if (logr == LR && (int)a.logc == LC && tile_cfg_matches(a, LR, LC, KD)) {                      \
-    tile_body<LR, INV, 0, TileCfg<LC, KD>, FLD>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier);      \
-    g_cfg_used = KD;                                                                             \
-    return true;                                                                                 \
-  }
-    RONK_CFG_TABLE(EMU_MONT_CASE)
-#undef EMU_MONT_CASE
-    return false;
-  } else {
-  if (half) {
-#define EMU_HALF_CASE(LR, LC, KD)                                                                \
-  if (logr == LR && (int)a.logc == LC && tile_cfg_matches(a, LR, LC, KD)) {                      \
-    tile_body<LR, INV, 0, TileCfg<LC, KD, false, true>>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); \
-    g_cfg_used = KD + 10;                                                                        \
-    return true;                                                                                 \
-  }
-    RONK_CFG_TABLE(EMU_HALF_CASE)
-#undef EMU_HALF_CASE
-  }
-  {
-    const int feat = tile_features(a);
-#define EMU_FEAT_CASE(LR, LC, KD, FT)                                                            \
-  if (logr == LR && (int)a.logc == LC && feat == FT && tile_cfg_matches(a, LR, LC, KD, FT)) {    \
-    tile_body<LR, INV, 0, TileCfg<LC, KD, false, false, FT>>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); \
-    g_cfg_used = KD + 100 * FT;                                                                  \
-    return true;                                                                                 \
-  }
-    RONK_CFG_TABLE_FEAT(EMU_FEAT_CASE)
+      RONK_CFG_TABLE_FEAT(EMU_FEAT_CASE)
 #undef EMU_FEAT_CASE
-    if (feat) return false;
+      return false;
+    case TileForm::HALF:
+    case TileForm::R4:   // (Goldilocks only)
+      if constexpr (!FLD::MONT) {
+#define EMU_HALF_R4_CASE(LR, LC, KD)                                                                                    \
+  if (logr == LR && logc == LC && c.kind == KD) {                                                                       \
+    if (c.form == TileForm::HALF) tile_body<LR, INV, 0, TileCfg<LC, KD, false, true>>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); \
+    else if constexpr (cfg_r4(LR, LC, KD))                                                                              \
+      tile_body<LR, INV, 0, TileCfg<LC, KD, false, false, 0, true>>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier);         \
+    else return false;                                                                                                  \
+    return true;                                                                                                        \
   }
-  // the R4 round structure of the 2^9 / 2^10-row shapes (tile_kernels_r4.hip; opt-in with RONK_R4MID=1 like the library)
-  static const bool r4_on = getenv("RONK_R4MID") && atoi(getenv("RONK_R4MID")) != 0;
-  if (r4_on && (logr == 9 || logr == 10)) {
-#define EMU_R4_CASE(LR, LC, KD)                                                                  \
-  if constexpr (cfg_r4(LR, LC, KD)) {                                                            \
-    if (logr == LR && (int)a.logc == LC && KD < 4 && tile_cfg_matches(a, LR, LC, KD)) {          \
-      tile_body<LR, INV, 0, TileCfg<LC, KD, false, false, 0, true>>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); \
-      g_cfg_used = KD + 20;                                                                      \
-      return true;                                                                               \
-    }                                                                                            \
+        RONK_CFG_TABLE(EMU_HALF_R4_CASE)
+#undef EMU_HALF_R4_CASE
+      }
+      return false;
+    case TileForm::CFG:
+#define EMU_CFG_CASE(LR, LC, KD)                                                                                        \
+  if (logr == LR && logc == LC && c.kind == KD) {                                                                       \
+    tile_body<LR, INV, 0, TileCfg<LC, KD, !FLD::MONT && cfg_ldstw(LR, LC, KD)>, FLD>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); \
+    return true;                                                                                                        \
   }
-    RONK_CFG_TABLE(EMU_R4_CASE)
-#undef EMU_R4_CASE
-  }
-#define EMU_CFG_CASE(LR, LC, KD)                                                                 \
-  if (logr == LR && (int)a.logc == LC && tile_cfg_matches(a, LR, LC, KD)) {                      \
-    tile_body<LR, INV, 0, TileCfg<LC, KD, cfg_ldstw(LR, LC, KD)>>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); \
-    g_cfg_used = KD;                                                                             \
-    return true;                                                                                 \
-  }
-  RONK_CFG_TABLE(EMU_CFG_CASE)
-  RONK_CFG_TABLE_DIST(EMU_CFG_CASE)
+      RONK_CFG_TABLE(EMU_CFG_CASE)
+      if constexpr (!FLD::MONT) { RONK_CFG_TABLE_DIST(EMU_CFG_CASE) }
 #undef EMU_CFG_CASE
+      return false;
+    case TileForm::GENERIC:
+      switch (logr) {
+#define EMU_GENERIC_CASE(LR) case LR: tile_body<LR, INV, 0, TileCfg<-1, 0>, FLD>(a, g_fa.lds, tid, g_fa.bid, fiber_barrier); return true;
+        EMU_GENERIC_CASE(4) EMU_GENERIC_CASE(5) EMU_GENERIC_CASE(6) EMU_GENERIC_CASE(7) EMU_GENERIC_CASE(8) EMU_GENERIC_CASE(9)
+        EMU_GENERIC_CASE(10) EMU_GENERIC_CASE(11) EMU_GENERIC_CASE(12)
+#undef EMU_GENERIC_CASE
+      }
+  }
   return false;
-  }
-}
-
-template <bool INV, class FLD>
-static void dispatch_small(int logr, u32 tid) {
-  switch (logr) {
-#define EMU_SMALL_CASE(LR) case LR: small_body<LR, INV, FLD>(*g_fa.a, g_fa.lds, tid, g_fa.bid, fiber_barrier); break;
-    EMU_SMALL_CASE(4) EMU_SMALL_CASE(5) EMU_SMALL_CASE(6) EMU_SMALL_CASE(7) EMU_SMALL_CASE(8) EMU_SMALL_CASE(9) EMU_SMALL_CASE(10)
-#undef EMU_SMALL_CASE
-    default: abort();
-  }
 }
 
 template <bool INV, class FLD>
 static void dispatch(int logr, u32 tid) {
-  if (g_fa.small) { dispatch_small<INV, FLD>(logr, tid); return; }
-  if (!getenv("RONK_NO_CFG_KERNELS") && dispatch_cfg<INV, FLD>(logr, tid)) return;
-  switch (logr) {
-    case 4: run_body<4, INV, FLD>(tid); break;
-    case 5: run_body<5, INV, FLD>(tid); break;
-    case 6: run_body<6, INV, FLD>(tid); break;
-    case 7: run_body<7, INV, FLD>(tid); break;
-    case 8: run_body<8, INV, FLD>(tid); break;
-    case 9: run_body<9, INV, FLD>(tid); break;
-    case 10: run_body<10, INV, FLD>(tid); break;
-    case 11: run_body<11, INV, FLD>(tid); break;
-    case 12: run_body<12, INV, FLD>(tid); break;
-    default: abort();
+  if (g_fa.small) {
+    switch (logr) {
+#define EMU_SMALL_CASE(LR) case LR: small_body<LR, INV, FLD>(*g_fa.a, g_fa.lds, tid, g_fa.bid, fiber_barrier); return;
+      EMU_SMALL_CASE(4) EMU_SMALL_CASE(5) EMU_SMALL_CASE(6) EMU_SMALL_CASE(7) EMU_SMALL_CASE(8) EMU_SMALL_CASE(9) EMU_SMALL_CASE(10)
+#undef EMU_SMALL_CASE
+    }
+    abort();
   }
+  if (!run_choice<INV, FLD>(logr, tid)) abort();   // the launcher would fail the same way: no such instantiation
 }
 
 static void fiber_main(int tid) {
@@ -210,6 +156,17 @@ static void run_block(u32 T) {
   }
 }
 
+// one pass: the body select_tile picks for it (the latency form: small), every workgroup of the grid one after the other
+static TileChoice run_pass(const PassDesc& p, const TileArgs& a, bool inv, std::vector<u64>& lds) {
+  const TileChoice c = p.small ? TileChoice{} : select_tile(a, p.logr, inv, p.grid, p.block, tile_env());
+  lds.assign(p.lds_bytes / 8 + 1 + ((size_t)1 << p.logr), 0);   // + room for the LDS-staged round twiddles
+  for (u32 bid = 0; bid < p.grid; bid++) {
+    g_fa = FiberArgs{&a, lds.data(), bid, p.logr, inv, p.small, c};
+    run_block(p.block);
+  }
+  return c;
+}
+
 static u64 splitmix(u64& s) {
   s += 0x9E3779B97F4A7C15ull;
   u64 z = s;
@@ -235,13 +192,7 @@ static void run_plan(const PlanDesc& pd, bool inv, const u64* in, u64* out, u64*
     a.wr = pd.wr[p.wr_id].data();
     if (p.tw_id >= 0) { a.tw_lo = pd.tw[p.tw_id].lo.data(); a.tw_hi = pd.tw[p.tw_id].hi.data(); }
     if (p.twf_id >= 0) a.tw_full = pd.twf[p.twf_id].data();
-    lds.assign(p.lds_bytes / 8 + 1 + ((size_t)1 << p.logr), 0);   // + room for the LDS-staged round twiddles
-    g_cfg_used = 0;
-    for (u32 bid = 0; bid < p.grid; bid++) {
-      g_fa.a = &a; g_fa.lds = lds.data(); g_fa.bid = bid; g_fa.logr = p.logr; g_fa.inv = inv; g_fa.small = p.small;
-      run_block(p.block);
-    }
-    (g_cfg_used ? g_dist_cfg : g_dist_generic)++;
+    (run_pass(p, a, inv, lds).form != TileForm::GENERIC ? g_dist_cfg : g_dist_generic)++;
   }
 }
 
@@ -351,12 +302,7 @@ static int mul_main(int log2n, u64 d, u64 d2, int logc, int inv_twf) {
   {   // F1: column pass of the batch of two, padding limits d / d2
     TileArgs a = bind_pass(F, 0, ab.data(), nullptr, ftmp.data());
     a.in_valid = d; a.in_valid1 = d2;
-    const PassDesc& p = F.passes[0];
-    lds.assign(p.lds_bytes / 8 + 1 + ((size_t)1 << p.logr), 0);
-    for (u32 bid = 0; bid < p.grid; bid++) {
-      g_fa.a = &a; g_fa.lds = lds.data(); g_fa.bid = bid; g_fa.logr = p.logr; g_fa.inv = false; g_fa.small = p.small;
-      run_block(p.block);
-    }
+    run_pass(F.passes[0], a, false, lds);
   }
   TileArgs fa = bind_pass(F, 1, nullptr, nullptr, ftmp.data()), ia = bind_pass(I, 0, nullptr, nullptr, itmp.data());
   const int kindi = ia.tw_full ? 3 : 1, logr = F.passes[1].logr;
@@ -369,12 +315,7 @@ static int mul_main(int log2n, u64 d, u64 d2, int logc, int inv_twf) {
   {   // I2: the inverse's row pass, output truncated to d + d2 - 1 coefficients
     TileArgs a = bind_pass(I, 1, nullptr, out.data(), itmp.data());
     a.out_valid = m;
-    const PassDesc& p = I.passes[1];
-    lds.assign(p.lds_bytes / 8 + 1 + ((size_t)1 << p.logr), 0);
-    for (u32 bid = 0; bid < p.grid; bid++) {
-      g_fa.a = &a; g_fa.lds = lds.data(); g_fa.bid = bid; g_fa.logr = p.logr; g_fa.inv = true; g_fa.small = p.small;
-      run_block(p.block);
-    }
+    run_pass(I.passes[1], a, true, lds);
   }
   // the oracle: NTT product of the zero-padded operands (the schoolbook Mul is O(d * d2); at these sizes the two agree by
   // tests/test_oracle_golden.py) -- three oracle transforms
@@ -405,7 +346,10 @@ int main(int argc, char** argv) {
   if (argc >= 6 && !strcmp(argv[1], "dist")) g_twf = atoi(argv[5]);
   if (argc >= 5 && !strcmp(argv[1], "dist"))   // emu_tile dist <log2n> <world> <inverse> [twf_max_log] [chunks]
     return dist_main(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]) != 0, argc >= 7 ? atoi(argv[6]) : 1);
-  if (argc < 5) { fprintf(stderr, "usage: emu_tile log2n batch inverse max_logc\n"); return 2; }
+  // emu_tile select <same arguments>: the plan's pass lines only (which body runs each pass), nothing executed
+  const bool select_only = argc >= 2 && !strcmp(argv[1], "select");
+  if (select_only) { argc--; argv++; }
+  if (argc < 5) { fprintf(stderr, "usage: emu_tile [select] log2n batch inverse max_logc\n"); return 2; }
   int log2n = atoi(argv[1]);
   u64 batch = strtoull(argv[2], 0, 10);
   bool inv = atoi(argv[3]) != 0;
@@ -420,15 +364,13 @@ int main(int argc, char** argv) {
   const bool twf_t = getenv("RONK_TWF_T") && atoi(getenv("RONK_TWF_T")) != 0;   // the full twiddle matrix transposed (plan.h)
   PlanDesc pd = build_plan(log2n, batch, inv, max_logc, twf, three_from, auto_tiles, 0, g_hf, twf_t);
 
-  std::vector<u64> in(n * batch), out(n * batch, 0xDEADBEEFull), tmp(n * batch, 0xDEADBEEFull), ref(n * batch);
+  const u64 len = select_only ? 0 : n * batch;
+  std::vector<u64> in(len), out(len, 0xDEADBEEFull), tmp(len, 0xDEADBEEFull), ref(len), in2(with_in2 ? std::max<u64>(len, 1) : 0);
   u64 s = 0x5EED0000ull + log2n;
   for (auto& v : in) v = rnd_elem(s);
   // adversarial corners
-  in[0] = g_p - 1; if (n > 1) in[n - 1] = g_p - 1; if (n > 2) in[1] = 0;
-
-  std::vector<u64> in2;
-  if (with_in2) {
-    in2.resize(n * batch);
+  if (len) { in[0] = g_p - 1; if (n > 1) in[n - 1] = g_p - 1; if (n > 2) in[1] = 0; }
+  if (with_in2 && len) {
     for (auto& v : in2) v = rnd_elem(s);
     in2[0] = g_p - 1; in2[n - 1] = 0;
   }
@@ -446,18 +388,12 @@ int main(int argc, char** argv) {
     if (in_valid && p.in_buf == BUF_IN) a.in_valid = in_valid;
     if (in_valid1 && p.in_buf == BUF_IN) a.in_valid1 = in_valid1;
     if (out_valid && p.out_buf == BUF_OUT) a.out_valid = out_valid;
-    lds.assign(p.lds_bytes / 8 + 1 + ((size_t)1 << p.logr), 0);   // + room for the LDS-staged round twiddles
-    g_cfg_used = 0;
-    for (u32 bid = 0; bid < p.grid; bid++) {
-      g_fa.a = &a; g_fa.lds = lds.data(); g_fa.bid = bid; g_fa.logr = p.logr; g_fa.inv = inv; g_fa.small = p.small;
-      run_block(p.block);
-    }
+    const TileChoice c = select_only ? (p.small ? TileChoice{} : select_tile(a, p.logr, inv, p.grid, p.block, tile_env()))
+                                     : run_pass(p, a, inv, lds);
     printf("pass logr=%d logc=%u tiles=%u nb1=%u nb2=%u grid=%u block=%u lds=%zu kernel=%s\n", p.logr, a.logc, a.tiles,
-           a.nb1, a.nb2, p.grid, p.block, p.lds_bytes, g_cfg_used == 1 ? "cfg:column/two-level" : g_cfg_used == 3 ? "cfg:column/matrix" :
-           g_cfg_used == 2 ? "cfg:row" : g_cfg_used == 5 ? "cfg:whole" : g_cfg_used == 4 ? "cfg:general" : g_cfg_used == 11 ? "half:column/two-level" : g_cfg_used == 13 ? "half:column/matrix" :
-           g_cfg_used == 12 ? "half:row" : g_cfg_used == 31 ? "wl:column/two-level" : g_cfg_used == 33 ? "wl:column/matrix" : g_cfg_used == 32 ? "wl:row" : g_cfg_used == 21 ? "r4:column/two-level" : g_cfg_used == 23 ? "r4:column/matrix" : g_cfg_used == 22 ? "r4:row" : g_cfg_used >= 100 ? (g_cfg_used % 100 == 2 ? "feat:row" : g_cfg_used % 100 == 3 ? "feat:column/matrix" : "feat:column/two-level") :
-           p.small ? "small" : "generic");
+           a.nb1, a.nb2, p.grid, p.block, p.lds_bytes, p.small ? "small" : tile_choice_label(c));
   }
+  if (select_only) return 0;
   if (in_valid) for (u64 b = 0; b < batch; b++) for (u64 i = (b && in_valid1) ? in_valid1 : in_valid; i < n; i++) in[b * n + i] = 0;  // what the kernel must have seen
   if (with_in2) for (u64 i = 0; i < n * batch; i++) in[i] = orc_mul(g_p, in[i], in2[i]);
   for (u64 b = 0; b < batch; b++) {

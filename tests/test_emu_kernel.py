@@ -16,7 +16,7 @@ def emu():
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     srcs = [os.path.join(ROOT, "tests", "emu", "emu_tile.cpp")]
     deps = srcs + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("ntt_tile.h", "ntt_small.h", "ntt_mul.h", "plan.h", "gl64.h", "tile_cfg_table.h",
-                                                                                  "field_policy.h", "mont64.h", "ntt_tile_wl.h")]
+                                                                                  "field_policy.h", "mont64.h", "ntt_tile_wl.h", "tile_select.h")]
     if not os.path.exists(EXE) or any(os.path.getmtime(d) > os.path.getmtime(EXE) for d in deps):
         obj = os.path.join(ROOT, "build", "orc_emu.o")
         _build(["gcc", "-O2", "-c", "-o", obj, os.path.join(ROOT, "oracle", "ronk_oracle.c")], obj)
@@ -148,8 +148,8 @@ def test_fused_multiply_middle(emu, k, d, d2, logc, twf):
 
 
 def test_specialised_kernels_are_selected_and_generic_bodies_still_match(emu):
-    """the hot two-pass shapes run the compile-time-specialised bodies (tile_cfg_table.h; same selection rule as
-    tile_kernels.hip); with RONK_NO_CFG_KERNELS the generic body computes the same plans"""
+    """the hot two-pass shapes run the compile-time-specialised bodies (tile_cfg_table.h; the emulator and the library's
+    launch_tile share the selection rule, tile_select.h); with RONK_NO_CFG_KERNELS the generic body computes the same plans"""
     for args, kinds in (((22, 1, 0, 4), ("cfg:column/two-level", "cfg:row")), ((22, 1, 1, 2), ("wl:column/two-level", "wl:row")),
                         ((16, 3, 0, 4, 18), ("cfg:column/matrix", "cfg:row")), ((18, 1, 1, 4, 18), ("cfg:column/matrix", "cfg:row"))):
         out = subprocess.run([emu] + [str(a) for a in args], capture_output=True, text=True, timeout=600)
@@ -292,9 +292,11 @@ def test_paired_multiply_operands(emu, args):
 def test_three_pass_plans_run_the_specialised_bodies(emu, k, dirs):
     """2^23 .. : column pass (two-level twiddle) / middle pass (full matrix, one transform per row of the first split) /
     last pass (flat rows) all match a TileCfg shape now that nb2 is a run-time value there (2^25: the same shapes with 2^9
-    rows -- run on the GPU, too slow for the emulator in a CPU suite)"""
+    rows -- run on the GPU, too slow for the emulator in a CPU suite).  RONK_HALF_LDS=0: these grids are large enough for the
+    library's HALF rule (tile_select.h use_half), which tests/test_tile_select.py pins; here the full-image bodies are checked"""
     for inv in dirs:
-        out = subprocess.run([emu, str(k), "1", str(inv), "4", "18", "23"], capture_output=True, text=True, timeout=1800)
+        out = subprocess.run([emu, str(k), "1", str(inv), "4", "18", "23"], capture_output=True, text=True, timeout=1800,
+                             env=dict(os.environ, RONK_HALF_LDS="0"))
         lines = out.stdout.strip().splitlines()
         assert out.returncode == 0 and lines[-1].startswith("OK"), out.stdout[-400:]
         kinds = [l.split("kernel=")[1] for l in lines if l.startswith("pass")]

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ntt_tile_w.h"
+#include "../../ronkathon_amd/csrc/hip_launch.h"
 #include "../../ronkathon_amd/csrc/tile_launch.h"
 
 namespace ronk {
@@ -10,25 +11,12 @@ namespace ronk {
 template <bool INV, int KIND>
 __global__ void __launch_bounds__(512, 2) ntt_tile_w_kernel(const TileArgs a) {
   extern __shared__ __attribute__((aligned(16))) u64 lds[];
-  const u32 nb = gridDim.x, b = blockIdx.x;
-  const u32 q = nb >> 3, r = nb & 7, xcd = b & 7, idx = b >> 3;
-  const u32 bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  tile_body_w<INV, KIND>(a, lds, threadIdx.x, bid, [] { __syncthreads(); }, [] { __builtin_amdgcn_wave_barrier(); });
+  tile_body_w<INV, KIND>(a, lds, threadIdx.x, xcd_tile_id(), [] { __syncthreads(); }, [] { __builtin_amdgcn_wave_barrier(); });
 }
 
 template <bool INV, int KIND>
 static hipError_t launch_w(const TileArgs& a, u32 grid, hipStream_t s) {
-  static bool attr_done[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    e = hipFuncSetAttribute((const void*)ntt_tile_w_kernel<INV, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  hipLaunchKernelGGL((ntt_tile_w_kernel<INV, KIND>), dim3(grid), dim3(512), TW_LDS_BYTES, s, a);
-  return hipGetLastError();
+  return launch_dyn<ntt_tile_w_kernel<INV, KIND>>(grid, 512, TW_LDS_BYTES, s, a);
 }
 
 hipError_t launch_tile_w(int logr, bool inverse, int kind, const TileArgs& a, u32 grid, hipStream_t s, bool* found) {

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "../ronkathon_amd/csrc/hip_launch.h"
 #include "../ronkathon_amd/csrc/plan.h"
 #include "experiments/ntt_tile_w.h"
 
@@ -31,9 +32,7 @@ constexpr int NS = 24;   // u64 slots per wavefront record: [0] = count | hw_id 
 template <int LOGR, int LOGC, int KIND, bool HALF, bool FORCE>
 __global__ void __launch_bounds__(1024, HALF ? 8 : 4) stamp_kernel(const TileArgs a, u64* rec) {
   extern __shared__ __attribute__((aligned(16))) u64 lds[];
-  const u32 nb = gridDim.x, b = blockIdx.x;
-  const u32 q = nb >> 3, r = nb & 7, xcd = b & 7, idx = b >> 3;
-  const u32 bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const u32 bid = xcd_tile_id();
   typedef TileCfg<LOGC, KIND, false, HALF> CFG;
   u64 st[NS];
   int k = 2;
@@ -68,9 +67,7 @@ __global__ void __launch_bounds__(1024, HALF ? 8 : 4) stamp_kernel(const TileArg
 template <int KIND, bool FORCE>
 __global__ void __launch_bounds__(512, 2) stamp_kernel_w(const TileArgs a, u64* rec) {
   extern __shared__ __attribute__((aligned(16))) u64 lds[];
-  const u32 nb = gridDim.x, b = blockIdx.x;
-  const u32 q = nb >> 3, r = nb & 7, xcd = b & 7, idx = b >> 3;
-  const u32 bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const u32 bid = xcd_tile_id();
   u64 st[NS];
   int k = 2;
   st[k++] = wall_clock64();

@@ -9,6 +9,7 @@
 #include <functional>
 #include <vector>
 
+#include "../ronkathon_amd/csrc/hip_launch.h"
 #include "../ronkathon_amd/csrc/plan.h"
 
 using namespace ronk;
@@ -19,9 +20,7 @@ using namespace ronk;
 template <int LOGR, bool INV, int ABL, int LOGC = -1, int KIND = 0>
 __global__ void __launch_bounds__(1024) abl_kernel(const TileArgs a) {
   extern __shared__ __attribute__((aligned(16))) u64 lds[];
-  const u32 nb = gridDim.x, b = blockIdx.x;
-  const u32 q = nb >> 3, r = nb & 7, xcd = b & 7, idx = b >> 3;
-  const u32 bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const u32 bid = xcd_tile_id();
   tile_body<LOGR, INV, ABL, TileCfg<LOGC, KIND, cfg_ldstw(LOGR, LOGC, KIND)>>(a, lds, threadIdx.x, bid, [] { __syncthreads(); });
 }
 
@@ -190,9 +189,7 @@ static void two_pass_ablation(int log2n, u64 batch, int max_logc, u64** keep_in,
 template <int LOGR, int LOGC, int KIND>
 __global__ void __launch_bounds__(1024) stagger_kernel(const TileArgs a, int delay, u32* hist) {
   extern __shared__ __attribute__((aligned(16))) u64 lds[];
-  const u32 nb = gridDim.x, b = blockIdx.x;
-  const u32 q = nb >> 3, r = nb & 7, xcd = b & 7, idx = b >> 3;
-  const u32 bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  const u32 bid = xcd_tile_id();
   const u32 tg = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 16 << 6 | 4);   // HW_REG_HW_ID[19:16] = workgroup slot on the CU
   if (hist && threadIdx.x == 0) atomicAdd(&hist[tg & 15], 1u);
   if ((tg & 1) && delay > 0)
