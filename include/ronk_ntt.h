@@ -466,6 +466,67 @@ int ronk_sharded_mul_sync(ronk_sharded_mul_plan* plan);
 /* host pointers: a (d coefficients), b (d2) -> out (d + d2 - 1) = ronk_poly_mul; d + d2 - 1 > n is RONK_ERR_INVALID; synchronous */
 int ronk_poly_mul_sharded(ronk_sharded_mul_plan* plan, const uint64_t* a, size_t d, const uint64_t* b, size_t d2, uint64_t* out);
 
+/* ---- Poseidon over the 64-bit fields and a Merkle commitment on its sponge.
+ *      hashes::poseidon::{Poseidon, PoseidonSponge} (src/hashes/poseidon/mod.rs:56-149, sponge.rs:69-275), which the reference
+ *      keeps generic over `F: Field` with caller-supplied constants, and tree::merkle::MerkleTree (src/tree/merkle.rs:31-99) with
+ *      the sponge in the place of SHA-256.  Bit-exact restatement:
+ *        permutation  for r in 0 .. num_f + num_p: state[i] += rc[r * width + i]; x -> x^alpha on every element when
+ *                     r < num_f / 2 || r >= num_p + num_f / 2 (integer division: an odd num_f is legal), on state[0] otherwise;
+ *                     state = mds * state with the DENSE matrix in every round (the optimised sparse partial rounds change the
+ *                     caller's constants and are not offered).
+ *        sponge       capacity = width - rate, state ZERO; element i of a chunk is added to state[capacity + i]; a one-shot absorb
+ *                     of len elements runs ceil(len / rate) permutations, no padding, no length tag (len == 0: none, the squeeze
+ *                     returns zeros); squeezing reads state[capacity + k], k < rate, and permutes each time rate elements have
+ *                     been taken and more are wanted.
+ *        tree         leaf digest = sponge(leaf elements) squeezing digest_len; node = sponge(left || right); levels pair up
+ *                     from the left, an unpaired last node is hashed with itself; a proof is the sibling digests from the bottom
+ *                     up, the sibling's side given by the parity of the index.
+ *      The library ships NO parameter set: rc and mds come from the caller, as in the reference, and whether a given
+ *      (width, alpha, rounds, matrix) is secure for a given prime is the caller's concern.
+ *      Fields: Goldilocks (its own arithmetic) and any odd prime p < 2^64 (constants kept in Montgomery form on the device). */
+typedef struct ronk_poseidon ronk_poseidon;
+/* 2 <= width <= 16 (width < 2: RONK_ERR_INVALID, width > 16: RONK_ERR_UNSUPPORTED), 1 <= rate < width, alpha >= 1;
+ * rc: (num_f + num_p) * width words, mds: width * width words row-major, both reduced mod p on upload.  A composite p:
+ * RONK_ERR_NOT_PRIME (the test of ronk_check_prime); p == 2: RONK_ERR_UNSUPPORTED.  The handle lives on the current device. */
+int ronk_poseidon_create(ronk_poseidon** out, uint64_t p, uint32_t width, uint64_t alpha, uint32_t num_p, uint32_t num_f,
+                         uint32_t rate, const uint64_t* rc, const uint64_t* mds);
+int ronk_poseidon_destroy(ronk_poseidon* h);
+/* `count` states of `width` words each, row-major, permuted in place (a batch of Poseidon::hash, whose result is word 1). */
+int ronk_poseidon_permute_dev(const ronk_poseidon* h, uint64_t* d_states, size_t count, void* stream);
+/* Poseidon::hash on host pointers: `in` (len <= width words, else RONK_ERR_INDEX) padded with ZERO; out_state: the whole state. */
+int ronk_poseidon_hash(const ronk_poseidon* h, const uint64_t* in, size_t len, uint64_t* out_state);
+/* One sponge per item: element j of item i is d_in[i * item_stride + j * elem_stride]; d_out is n_items x n_out, row-major.
+ * (item_stride, elem_stride) = (1, N) hashes the columns of a row-major [len][N] matrix -- what ronk_lde_batch_dev and
+ * ronk_rs_encode_batch_dev leave behind -- with coalesced loads; (len, 1) is contiguous items.  Inputs >= p are reduced. */
+int ronk_poseidon_sponge_dev(const ronk_poseidon* h, const uint64_t* d_in, size_t n_items, size_t len, size_t item_stride,
+                             size_t elem_stride, uint64_t* d_out, size_t n_out, void* stream);
+/* Layout of a tree: level 0 = the n_leaves leaf digests, level l + 1 = ceil(count_l / 2) nodes, the root last, digest_len words
+ * per node.  ronk_merkle_level_offset: word offset of `level` (level = number of levels: the total, = ronk_merkle_tree_words). */
+size_t ronk_merkle_tree_words(size_t n_leaves, size_t digest_len);
+size_t ronk_merkle_level_offset(size_t n_leaves, size_t digest_len, size_t level);
+/* MerkleTree::new: writes every level into the caller-owned d_tree (ronk_merkle_tree_words words).  Leaves are addressed as the
+ * items of ronk_poseidon_sponge_dev; 1 <= digest_len <= rate and n_leaves >= 1, else RONK_ERR_INVALID.  Asynchronous, and it
+ * uses NO library workspace, so it is legal under stream capture. */
+int ronk_merkle_commit_dev(const ronk_poseidon* h, const uint64_t* d_leaves, size_t n_leaves, size_t leaf_len, size_t item_stride,
+                           size_t elem_stride, size_t digest_len, uint64_t* d_tree, void* stream);
+/* MerkleTree::get_proof for n_idx indices: d_paths is n_idx x depth x digest_len (depth = number of levels - 1; 0 for one leaf:
+ * the leaf digest is the root).  d_status[q] = 0, or RONK_ERR_INDEX for index >= n_leaves and for the unpaired last node of an
+ * odd level on the way up, where the reference indexes level[index + 1] out of bounds; that path is zero-filled. */
+int ronk_merkle_open_dev(const uint64_t* d_tree, size_t n_leaves, size_t digest_len, const uint64_t* d_indices, size_t n_idx,
+                         uint64_t* d_paths, int* d_status, void* stream);
+/* MerkleTree::prove, one query per lane: d_ok[q] = 1 when the digest of leaf q (n_idx items, addressed as above), folded with
+ * its path by the parity of d_indices[q], equals d_root (canonical words); else 0. */
+int ronk_merkle_verify_dev(const ronk_poseidon* h, const uint64_t* d_leaves, size_t n_idx, size_t leaf_len, size_t item_stride,
+                           size_t elem_stride, const uint64_t* d_indices, const uint64_t* d_paths, size_t n_leaves, size_t digest_len,
+                           const uint64_t* d_root, int* d_ok, void* stream);
+/* Host-pointer forms: contiguous leaves (n x leaf_len), synchronous.  ronk_merkle_open reads a HOST tree (no device work). */
+int ronk_merkle_commit(const ronk_poseidon* h, const uint64_t* leaves, size_t n_leaves, size_t leaf_len, size_t digest_len,
+                       uint64_t* tree);
+int ronk_merkle_open(const uint64_t* tree, size_t n_leaves, size_t digest_len, const uint64_t* indices, size_t n_idx, uint64_t* paths,
+                     int* status);
+int ronk_merkle_verify(const ronk_poseidon* h, const uint64_t* leaves, size_t n_idx, size_t leaf_len, const uint64_t* indices,
+                       const uint64_t* paths, size_t n_leaves, size_t digest_len, const uint64_t* root, int* ok);
+
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);
 int ronk_dev_free(void* ptr);

@@ -148,6 +148,19 @@ _SIG = {
     "ronk_poly_mul_sharded_dev": (_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "ronk_sharded_mul_sync": (_int, [_vp]),
     "ronk_poly_mul_sharded": (_int, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "ronk_poseidon_create": (_int, [C.POINTER(_vp), _u64, C.c_uint32, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "ronk_poseidon_destroy": (_int, [_vp]),
+    "ronk_poseidon_permute_dev": (_int, [_vp, _vp, _sz, _vp]),
+    "ronk_poseidon_hash": (_int, [_vp, _vp, _sz, _vp]),
+    "ronk_poseidon_sponge_dev": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _sz, _vp]),
+    "ronk_merkle_tree_words": (_sz, [_sz, _sz]),
+    "ronk_merkle_level_offset": (_sz, [_sz, _sz, _sz]),
+    "ronk_merkle_commit_dev": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "ronk_merkle_open_dev": (_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "ronk_merkle_verify_dev": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    "ronk_merkle_commit": (_int, [_vp, _vp, _sz, _sz, _sz, _vp]),
+    "ronk_merkle_open": (_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "ronk_merkle_verify": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp]),
     "ronk_dev_alloc": (_int, [C.POINTER(_vp), _sz]),
     "ronk_dev_free": (_int, [_vp]),
     "ronk_memcpy_h2d": (_int, [_vp, _vp, _sz]),
@@ -279,6 +292,61 @@ class Plan:
         ms = (C.c_float * np_)()
         check(lib.ronk_plan_time_passes(self.h, d_in, d_out, int(inverse), iters, ms, stream))
         return [float(v) for v in ms]
+
+
+class PoseidonHandle:
+    """ronk_poseidon: one parameter set (p, width, alpha, rounds, rate, rc, mds) resident on the current device.  The _dev
+    methods take raw device pointers (int) and enqueue on `stream`."""
+
+    def __init__(self, p, width, alpha, num_p, num_f, rate, rc, mds):
+        rc = arr([int(v) % p for v in rc])
+        mds = arr([int(v) % p for row in mds for v in row])
+        if rc.size != (num_p + num_f) * width or mds.size != width * width:
+            raise RonkPanic(ERR_INVALID, "rc holds (num_f + num_p) * width words, mds width * width")
+        self.h = _vp()
+        check(lib.ronk_poseidon_create(C.byref(self.h), p, width, alpha, num_p, num_f, rate, ptr(rc), ptr(mds)))
+        self.p, self.width, self.rate = p, width, rate
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib.ronk_poseidon_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def hash_state(self, values):
+        """Poseidon::hash's final state for `values` padded with ZERO (word 1 is the reference's return value)"""
+        v = arr([int(x) for x in values])
+        out = np.empty(self.width, dtype=np.uint64)
+        check(lib.ronk_poseidon_hash(self.h, ptr(v) if v.size else None, v.size, ptr(out)))
+        return out
+
+    def permute_dev(self, d_states, count, stream=0):
+        check(lib.ronk_poseidon_permute_dev(self.h, d_states, count, stream))
+
+    def sponge_dev(self, d_in, n_items, length, item_stride, elem_stride, d_out, n_out, stream=0):
+        check(lib.ronk_poseidon_sponge_dev(self.h, d_in, n_items, length, item_stride, elem_stride, d_out, n_out, stream))
+
+    def merkle_commit_dev(self, d_leaves, n_leaves, leaf_len, item_stride, elem_stride, digest_len, d_tree, stream=0):
+        check(lib.ronk_merkle_commit_dev(self.h, d_leaves, n_leaves, leaf_len, item_stride, elem_stride, digest_len, d_tree, stream))
+
+    def merkle_verify_dev(self, d_leaves, n_idx, leaf_len, item_stride, elem_stride, d_indices, d_paths, n_leaves, digest_len, d_root,
+                          d_ok, stream=0):
+        check(lib.ronk_merkle_verify_dev(self.h, d_leaves, n_idx, leaf_len, item_stride, elem_stride, d_indices, d_paths, n_leaves,
+                                         digest_len, d_root, d_ok, stream))
+
+
+def merkle_tree_words(n_leaves, digest_len):
+    return lib.ronk_merkle_tree_words(n_leaves, digest_len)
+
+
+def merkle_level_offset(n_leaves, digest_len, level):
+    return lib.ronk_merkle_level_offset(n_leaves, digest_len, level)
+
+
+def merkle_open_dev(d_tree, n_leaves, digest_len, d_indices, n_idx, d_paths, d_status, stream=0):
+    check(lib.ronk_merkle_open_dev(d_tree, n_leaves, digest_len, d_indices, n_idx, d_paths, d_status, stream))
 
 
 class ShardedPlan:

@@ -4,6 +4,7 @@
   K-coefficient message at omega_N^i, i < N, is a size-N DFT of the zero-padded message.
 * KZG `open` quotient (reference src/kzg/setup.rs:63-78): poly / (x - z).
 * KZG `commit` / `open` (reference src/kzg/setup.rs:45-78): the multi-scalar multiplication over the SRS.
+* `Poseidon`, `PoseidonSponge` (reference src/hashes/poseidon) and `MerkleTree` (reference src/tree/merkle.rs, over the sponge).
 """
 import ctypes as C
 
@@ -146,3 +147,116 @@ def kzg_open_bn254(coeffs, z, srs):
     x = sum(int(out[i]) << (64 * i) for i in range(4))
     y = sum(int(out[4 + i]) << (64 * i) for i in range(4))
     return (None if x == 0 and y == 0 else (x, y)), sum(int(val[i]) << (64 * i) for i in range(4))
+
+
+class Poseidon:
+    """`Poseidon<F>` (hashes/poseidon/mod.rs:56-149) over a 64-bit prime field, constants from the caller."""
+
+    def __init__(self, field, width, alpha, num_p, num_f, rc, mds, rate=None):
+        self.field = field
+        self.width = width
+        self.handle = L.PoseidonHandle(field.ORDER, width, alpha, num_p, num_f, rate if rate is not None else width - 1, rc, mds)
+
+    def hash(self, values):
+        """`Poseidon::hash`: the input padded with ZERO, permuted; returns state[1]."""
+        return int(self.handle.hash_state(values)[1])
+
+    def permute(self, values):
+        """the whole state after `Poseidon::hash`"""
+        return [int(v) for v in self.handle.hash_state(values)]
+
+
+def _dev_copy(a):
+    """host array -> a fresh device buffer (freed by the caller with ronk_dev_free)"""
+    d = C.c_void_p()
+    L.check(L.lib.ronk_dev_alloc(C.byref(d), max(a.nbytes, 8)))
+    if a.nbytes:
+        L.check(L.lib.ronk_memcpy_h2d(d, L.ptr(a), a.nbytes))
+    return d
+
+
+class PoseidonSponge:
+    """`PoseidonSponge<F, _>` (hashes/poseidon/sponge.rs:69-275), one-shot: absorb any number of times, then squeeze once.  The
+    absorbed elements are kept on the host and hashed by one device call at the squeeze (absorbing in pieces equals absorbing
+    the concatenation)."""
+
+    def __init__(self, field, width, alpha, num_p, num_f, rate, rc, mds):
+        self.field, self.rate = field, rate
+        self.handle = L.PoseidonHandle(field.ORDER, width, alpha, num_p, num_f, rate, rc, mds)
+        self._data = []
+        self._squeezed = False
+
+    def absorb(self, elements):
+        if self._squeezed:
+            raise L.RonkPanic(L.ERR_INVALID, "sponge is in squeezing state")
+        self._data.extend(int(v) % self.field.ORDER for v in elements)
+        return self
+
+    def squeeze(self, n):
+        if self._squeezed:
+            raise L.RonkPanic(L.ERR_UNSUPPORTED, "one squeeze per sponge")
+        self._squeezed = True
+        x = L.arr(self._data)
+        out = np.zeros(n, dtype=np.uint64)
+        if n == 0:
+            return []
+        d_in, d_out = _dev_copy(x), _dev_copy(out)
+        try:
+            self.handle.sponge_dev(d_in, 1, x.size, x.size, 1, d_out, n)
+            L.check(L.lib.ronk_dev_sync())
+            L.check(L.lib.ronk_memcpy_d2h(L.ptr(out), d_out, out.nbytes))
+        finally:
+            L.lib.ronk_dev_free(d_in); L.lib.ronk_dev_free(d_out)
+        return [int(v) for v in out]
+
+
+class MerkleTree:
+    """`MerkleTree` (tree/merkle.rs:31-99) with the Poseidon sponge as its hash: `leaves` is a sequence of equally long
+    sequences of field elements.  The tree is built on the device (ronk_merkle_commit) and kept on the host."""
+
+    def __init__(self, sponge_params, leaves, digest_len):
+        """sponge_params: (field, width, alpha, num_p, num_f, rate, rc, mds), as for PoseidonSponge"""
+        field = sponge_params[0]
+        self.field = field
+        self.handle = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
+        lv = L.arr([[int(v) % field.ORDER for v in leaf] for leaf in leaves])
+        if lv.ndim != 2 or lv.shape[0] == 0:
+            raise L.RonkPanic(L.ERR_INVALID, "a tree has at least one leaf, all of one length")
+        self.n, self.leaf_len, self.digest_len = lv.shape[0], lv.shape[1], digest_len
+        self.tree = np.empty(L.merkle_tree_words(self.n, digest_len), dtype=np.uint64)
+        L.check(L.lib.ronk_merkle_commit(self.handle.h, L.ptr(lv), self.n, self.leaf_len, digest_len, L.ptr(self.tree)))
+
+    def depth(self):
+        """number of levels above the leaves = length of a proof"""
+        depth = 0
+        while L.merkle_level_offset(self.n, self.digest_len, depth + 1) < self.tree.size:
+            depth += 1
+        return depth
+
+    def root_hash(self):
+        return [int(v) for v in self.tree[-self.digest_len:]]
+
+    def get_proof(self, leaf_index):
+        """-> list of (sibling digest, side) from the bottom up, side 'L' / 'R' as the reference's LeftOrRight; the reference's
+        out-of-bounds panic (index >= n, or the unpaired last node of an odd level) raises RonkPanic(ERR_INDEX)."""
+        depth = self.depth()
+        idx = L.arr([leaf_index]); path = np.zeros(max(depth * self.digest_len, 1), dtype=np.uint64)
+        st = (C.c_int * 1)()
+        L.check(L.lib.ronk_merkle_open(L.ptr(self.tree), self.n, self.digest_len, L.ptr(idx), 1, L.ptr(path), st))
+        L.check(st[0])
+        d = self.digest_len
+        return [([int(v) for v in path[l * d:(l + 1) * d]], "L" if (leaf_index >> l) & 1 else "R") for l in range(depth)]
+
+    def prove(self, leaf, proof):
+        """`MerkleTree::prove`: folds the leaf's digest with the proof and compares with the root.  The sides of the proof give
+        the index (bit l = 1 when the sibling is on the left)."""
+        if len(proof) != self.depth() or any(len(sib) != self.digest_len for sib, _ in proof):
+            return False
+        index = sum(1 << l for l, (_, side) in enumerate(proof) if side == "L")
+        lv = L.arr([int(v) % self.field.ORDER for v in leaf])
+        path = L.arr([v for sib, _ in proof for v in sib]) if proof else np.zeros(1, dtype=np.uint64)
+        root = L.arr(self.root_hash())
+        idx = L.arr([index]); ok = (C.c_int * 1)()
+        L.check(L.lib.ronk_merkle_verify(self.handle.h, L.ptr(lv), 1, lv.size, L.ptr(idx), L.ptr(path), self.n, self.digest_len,
+                                         L.ptr(root), ok))
+        return bool(ok[0])

@@ -269,6 +269,81 @@ struct AffinePoint {                       // Point(x, y) with x = x0 + x1 t, y 
   friend bool operator==(const AffinePoint& a, const AffinePoint& b) { return a.w == b.w; }
 };
 inline const ronk_curve& PlutoExtendedCurve() { static const ronk_curve c{101, 99, 0, 3}; return c; }   // pluto_curve.rs:39-51
+// ---- Poseidon over a 64-bit prime field and a Merkle tree on its sponge (hashes/poseidon/mod.rs:56-149, sponge.rs:69-275,
+// tree/merkle.rs:31-99 with the sponge as the hash).  Constants come from the caller, as in the reference.
+template <class F> class Poseidon {
+ public:
+  Poseidon(size_t width, size_t alpha, size_t num_p, size_t num_f, size_t rate, const std::vector<F>& rc, const std::vector<F>& mds)
+      : width_(width), rate_(rate) {
+    if (rc.size() != (num_p + num_f) * width || mds.size() != width * width) throw Panic(RONK_ERR_INVALID);
+    check(ronk_poseidon_create(&h_, F::ORDER, (uint32_t)width, alpha, (uint32_t)num_p, (uint32_t)num_f, (uint32_t)rate,
+                               reinterpret_cast<const uint64_t*>(rc.data()), reinterpret_cast<const uint64_t*>(mds.data())));
+  }
+  Poseidon(const Poseidon&) = delete;
+  Poseidon& operator=(const Poseidon&) = delete;
+  ~Poseidon() { if (h_) ronk_poseidon_destroy(h_); }
+  const ronk_poseidon* raw() const { return h_; }
+  size_t width() const { return width_; }
+  size_t rate() const { return rate_; }
+  // Poseidon::hash: pad with ZERO, permute, state[1]
+  F hash(const std::vector<F>& state) const {
+    std::vector<F> out(width_);
+    check(ronk_poseidon_hash(h_, state.empty() ? nullptr : reinterpret_cast<const uint64_t*>(state.data()), state.size(),
+                             reinterpret_cast<uint64_t*>(out.data())));
+    return out[1];
+  }
+
+ private:
+  ronk_poseidon* h_ = nullptr;
+  size_t width_, rate_;
+};
+
+enum class LeftOrRight { Left, Right };
+// MerkleTree over a Poseidon sponge: leaves are n x leaf_len field elements, row-major; every level is kept (leaves first)
+template <class F> class MerkleTree {
+ public:
+  using Proof = std::vector<std::pair<std::vector<F>, LeftOrRight>>;
+  MerkleTree(const Poseidon<F>& hasher, const std::vector<F>& leaves, size_t leaf_len, size_t digest_len)
+      : hasher_(hasher), n_(leaf_len ? leaves.size() / leaf_len : 0), d_(digest_len), tree_(ronk_merkle_tree_words(n_, d_)) {
+    check(ronk_merkle_commit(hasher.raw(), reinterpret_cast<const uint64_t*>(leaves.data()), n_, leaf_len, d_,
+                             reinterpret_cast<uint64_t*>(tree_.data())));
+  }
+  size_t depth() const { size_t l = 0; while (ronk_merkle_level_offset(n_, d_, l + 1) < tree_.size()) l++; return l; }
+  std::vector<F> root_hash() const { return std::vector<F>(tree_.end() - d_, tree_.end()); }
+  // throws RONK_ERR_INDEX where the reference's get_proof indexes out of bounds
+  Proof get_proof(size_t leaf_index) const {
+    const size_t dep = depth();
+    std::vector<F> path(dep * d_ + 1);
+    uint64_t idx = leaf_index; int status = 0;
+    check(ronk_merkle_open(reinterpret_cast<const uint64_t*>(tree_.data()), n_, d_, &idx, 1, reinterpret_cast<uint64_t*>(path.data()), &status));
+    check(status);
+    Proof pr;
+    for (size_t l = 0; l < dep; l++)
+      pr.push_back({std::vector<F>(path.begin() + l * d_, path.begin() + (l + 1) * d_), ((leaf_index >> l) & 1) ? LeftOrRight::Left : LeftOrRight::Right});
+    return pr;
+  }
+  bool prove(const std::vector<F>& leaf, const Proof& proof) const {
+    if (proof.size() != depth()) return false;
+    uint64_t idx = 0;
+    std::vector<F> path;
+    for (size_t l = 0; l < proof.size(); l++) {
+      if (proof[l].first.size() != d_) return false;
+      if (proof[l].second == LeftOrRight::Left) idx |= (uint64_t)1 << l;
+      path.insert(path.end(), proof[l].first.begin(), proof[l].first.end());
+    }
+    if (path.empty()) path.resize(1);
+    int ok = 0;
+    check(ronk_merkle_verify(hasher_.raw(), reinterpret_cast<const uint64_t*>(leaf.data()), 1, leaf.size(), &idx,
+                             reinterpret_cast<const uint64_t*>(path.data()), n_, d_, reinterpret_cast<const uint64_t*>(&*(tree_.end() - d_)), &ok));
+    return ok == 1;
+  }
+
+ private:
+  const Poseidon<F>& hasher_;
+  size_t n_, d_;
+  std::vector<F> tree_;
+};
+
 namespace kzg {
 // commit(coeffs, g1_srs): SUM g1_srs[i] * coeffs[i]
 template <class S>

@@ -32,8 +32,10 @@ pub mod bn254;
 pub mod codes;
 pub mod device;
 pub mod ffi;
+pub mod ffi_hashes;
 pub mod ffi_sharded_mul;
 pub mod field;
+pub mod hashes;
 pub mod polynomial;
 pub mod prime64;
 

@@ -676,8 +676,44 @@ def sec_threads(deadline):
     counts["threads"] = total[0]
 
 
+def sec_hash(deadline):
+    """Poseidon sponge (both stride layouts) and the Merkle commitment against the Python restatement (tests/poseidon_ref.py) with
+    random test parameters: field, width, rate, alpha, round counts, item length, output count, leaf count"""
+    import poseidon_ref as PR
+    it = 0
+    while time.time() < deadline:
+        it += 1
+        p = rng.choice([GP, GP, PR.MONT_P, 29 * 2**57 + 1, 101])
+        width = rng.randrange(2, 17)
+        rate = rng.randrange(1, width)
+        alpha = rng.choice([3, 5, 7, 11, 1, 17])
+        P = PR.derive_params(p, width, alpha, rng.randrange(0, 4), rng.randrange(1, 5), rate, seed=SEED * 7919 + it)
+        h = L.PoseidonHandle(*P.create_args())
+        items, length, n_out = rng.randrange(1, 6), rng.randrange(0, 3 * rate + 3), rng.randrange(1, rate + 4)
+        mat = edge_values(p, items * max(length, 1), it).reshape(items, max(length, 1))
+        want = [PR.sponge(P, [int(v) for v in mat[i, :length]], n_out) for i in range(items)]
+        for lay, (src, i_s, e_s) in enumerate(((mat, max(length, 1), 1), (mat.T.copy(), 1, items))):
+            out = torch.full((items * n_out,), -1, dtype=torch.int64, device="cuda")
+            d_in = dev(src)
+            h.sponge_dev(d_in.data_ptr(), items, length, i_s, e_s, out.data_ptr(), n_out)
+            torch.cuda.synchronize()
+            if host(out).reshape(items, n_out).tolist() != want:
+                report("hash", "sponge", p, width, rate, alpha, length, n_out, lay)
+        n, d, ll = rng.choice([1, 2, 3, 7, 40, 300]), rng.randrange(1, min(rate, 4) + 1), rng.randrange(1, 5)
+        leaves = edge_values(p, n * ll, it + 1)
+        ref = PR.MerkleTree(P, [[int(v) for v in leaves[i * ll:(i + 1) * ll]] for i in range(n)], d)
+        d_tree = torch.full((L.merkle_tree_words(n, d),), -1, dtype=torch.int64, device="cuda")
+        d_lv = dev(leaves)
+        h.merkle_commit_dev(d_lv.data_ptr(), n, ll, ll, 1, d, d_tree.data_ptr())
+        torch.cuda.synchronize()
+        if host(d_tree).tolist() != ref.flat():
+            report("hash", "merkle", p, width, rate, alpha, n, d, ll)
+        h.close()
+    counts["hash"] = it
+
+
 SECTIONS = dict(ntt=sec_ntt, mul=sec_mul, generic=sec_generic, mont=sec_mont, divrem=sec_divrem, lindiv=sec_lindiv, codes=sec_codes, vec=sec_vec,
-                lagrange=sec_lagrange, msm=sec_msm, sharded=sec_sharded, threads=sec_threads)
+                lagrange=sec_lagrange, msm=sec_msm, sharded=sec_sharded, threads=sec_threads, hash=sec_hash)
 
 
 def main():
