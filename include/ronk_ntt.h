@@ -254,6 +254,37 @@ int ronk_rs_encode_batch_dev(ronk_plan* plan, const uint64_t* d_msgs, size_t k, 
 #define RONK_ROOTS_LEAF 64
 int ronk_poly_from_roots(uint64_t p, const uint64_t* roots, size_t m, uint64_t* out);
 int ronk_poly_from_roots_dev(uint64_t p, const uint64_t* d_roots, size_t m, uint64_t* d_out, void* stream);
+/* One polynomial at many arbitrary points (Polynomial::evaluate in a loop: Shamir's split, src/shamir/mod.rs:33-60):
+ * out[i] = sum_j c[j] xs[i]^j as canonical residues, bit-identical to m calls of ronk_poly_eval.  Any points (reduced mod p;
+ * repeats and ZERO allowed), any d >= 1 and m >= 1; NULL pointers or zero sizes: RONK_ERR_INVALID.
+ * Tree form, O(m log^2 m + d log d): the product tree of ronk_poly_from_roots with every level retained, the inverse series of
+ * its reversed root by the Newton ladder of the fast division (precision max(d, Mp): a longer f needs no division), then the
+ * transposed walk down (csrc/multipoint_kernels.h) -- per level one batched forward transform of the windows and two inverses
+ * with the sibling's retained transform multiplied on load.  Fields: what ronk_poly_from_roots needs for m points AND the
+ * 2-adicity of the root's products, 2^(ceil(log2 max(d, Mp)) + 1) | p - 1 (Goldilocks always); m <= 2^24.
+ * Direct form, any odd prime: one batched Horner kernel, O(m d), the coefficients staged in LDS and shared by a workgroup's
+ * points; refused (RONK_ERR_UNSUPPORTED) beyond m d = 2^34.  The library picks the form at a measured crossover (DESIGN.md
+ * section 11); the environment variable RONK_MULTIPOINT_FORM = direct | tree forces one (A/B runs; a form that does not serve
+ * the call is then RONK_ERR_UNSUPPORTED).
+ * Workspace of the tree form, in words, from the event-guarded pool: (2 levels + 9) Mp + 10 Lp + 8, Mp = m padded to
+ * RONK_ROOTS_LEAF * 2^levels, Lp = the power of two >= max(d, Mp) -- (2 levels + 19) Mp + 8 for d <= Mp.
+ * Asynchronous on `stream`; not for hipGraph capture (RONK_ERR_UNSUPPORTED while capturing).  Tree-form calls serialise on the
+ * lock of ronk_poly_from_roots while they enqueue. */
+int ronk_poly_eval_many_dev(uint64_t p, const uint64_t* d_c, size_t d, const uint64_t* d_xs, size_t m, uint64_t* d_out,
+                            void* stream);
+int ronk_poly_eval_many(uint64_t p, const uint64_t* c, size_t d, const uint64_t* xs, size_t m, uint64_t* out);
+/* The m coefficients of the unique polynomial of degree < m through (xs[i], ys[i]) -- Lagrange interpolation through arbitrary
+ * coordinates (Message::decode, src/codes/reed_solomon.rs:55-107; Shamir's combine): the polynomial ronk_rs_decode returns,
+ * without its 2^14 limit.  Coincident nodes are the reference's `numerator / denominator` panic: the _dev form writes
+ * RONK_ERR_ZERO_INVERSE to *d_status (required; 0 otherwise, written by the call), the host form returns it.
+ * Tree form, O(m log^2 m): Z = prod (x - x_i) by the retained tree, Z'(x_i) by the walk of ronk_poly_eval_many on the same
+ * tree, w_i = y_i / Z'(x_i) by chunked batch inversion, then one more walk up, N_S = N_L M_R + N_R M_L on the retained
+ * transforms.  Fields as for the tree form above with d = m; m <= 2^24; workspace (2 levels + 21) Mp + 8 words.
+ * Direct form: the O(m^2) kernels of ronk_rs_decode_dev, any odd prime, m <= 2^14; beyond that without the 2-adicity:
+ * RONK_ERR_UNSUPPORTED.  Form choice, stream, capture and locking as above. */
+int ronk_poly_interpolate_dev(uint64_t p, const uint64_t* d_xs, const uint64_t* d_ys, size_t m, uint64_t* d_out, int* d_status,
+                              void* stream);
+int ronk_poly_interpolate(uint64_t p, const uint64_t* xs, const uint64_t* ys, size_t m, uint64_t* out);
 /* Reed-Solomon erasure decoding, the inverse of ronk_rs_encode_batch_dev (src/codes/reed_solomon.rs:42-106) on the same plan
  * (p, g, N = plan n >= 16, B = plan batch).  d_ys: B x N codeword values at x_i = omega_N^i.  d_erased: n_erased DISTINCT
  * positions (< N), shared by all B rows; their values in d_ys are ignored.  k == 0: RONK_ERR_INVALID; k > N or

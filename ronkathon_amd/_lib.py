@@ -105,6 +105,10 @@ _SIG = {
     "ronk_rs_encode_batch_dev": (_int, [_vp, _vp, _sz, _vp, _vp]),
     "ronk_poly_from_roots": (_int, [_u64, _vp, _sz, _vp]),
     "ronk_poly_from_roots_dev": (_int, [_u64, _vp, _sz, _vp, _vp]),
+    "ronk_poly_eval_many": (_int, [_u64, _vp, _sz, _vp, _sz, _vp]),
+    "ronk_poly_eval_many_dev": (_int, [_u64, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "ronk_poly_interpolate": (_int, [_u64, _vp, _vp, _sz, _vp]),
+    "ronk_poly_interpolate_dev": (_int, [_u64, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ronk_rs_recover_batch_dev": (_int, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "ronk_rs_recover": (_int, [_u64, _u64, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
     "ronk_lde_batch_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp]),

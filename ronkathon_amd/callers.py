@@ -70,6 +70,29 @@ def poly_from_roots(field, roots):
     return Polynomial.new(field, out)
 
 
+def poly_eval_many(field, coeffs, xs):
+    """[f(x) for x in xs] for f = sum coeffs[j] x^j: `Polynomial::evaluate` in a loop (Shamir's split, shamir/mod.rs:33-60) as one
+    call (ronk_poly_eval_many) -- the walk down the retained product tree of the points, or the batched Horner kernel."""
+    c = L.arr([int(v) % field.ORDER for v in coeffs]) if not isinstance(coeffs, np.ndarray) else L.arr(coeffs)
+    x = L.arr([int(v) % field.ORDER for v in xs]) if not isinstance(xs, np.ndarray) else L.arr(xs)
+    out = np.empty(x.size, dtype=np.uint64)
+    L.check(L.lib.ronk_poly_eval_many(field.ORDER, L.ptr(c) if c.size else None, c.size, L.ptr(x) if x.size else None, x.size, L.ptr(out)))
+    return out
+
+
+def poly_interpolate(field, xs, ys):
+    """The Polynomial of degree < m through the m coordinates (xs[i], ys[i]), any distinct nodes (ronk_poly_interpolate): Lagrange
+    interpolation as in Message::decode (codes/reed_solomon.rs:55-107) and Shamir's combine.  Coincident nodes raise
+    RonkPanic(ERR_ZERO_INVERSE), the reference's `numerator / denominator` panic."""
+    x = L.arr([int(v) % field.ORDER for v in xs]) if not isinstance(xs, np.ndarray) else L.arr(xs)
+    y = L.arr([int(v) % field.ORDER for v in ys]) if not isinstance(ys, np.ndarray) else L.arr(ys)
+    if x.size != y.size:
+        raise L.RonkPanic(L.ERR_INVALID, "one value per node")
+    out = np.empty(x.size, dtype=np.uint64)
+    L.check(L.lib.ronk_poly_interpolate(field.ORDER, L.ptr(x) if x.size else None, L.ptr(y) if y.size else None, x.size, L.ptr(out)))
+    return Polynomial.new(field, out)
+
+
 def kzg_open_quotient(field, coeffs, eval_point):
     """`kzg::open`'s polynomial step (kzg/setup.rs:63-78): Polynomial::new(coeffs).div([-z, 1])."""
     poly = Polynomial.new(field, coeffs)

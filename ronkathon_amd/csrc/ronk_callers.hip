@@ -613,7 +613,7 @@ __global__ void __launch_bounds__(256) dv_rem_kernel(Ops ops, const u64* __restr
 // (prime/mod.rs:197-201), and the caller needs no generator.  The prime must have the 2-adicity of the largest product
 // (2 * 2^ceil(log2 d) points).  Round 5 knew only Goldilocks here: every other field took the one-workgroup long division,
 // minutes at 2^22 by 2^21.
-static bool newton_field(const FieldCtx& f, size_t d, u64* g) {
+bool newton_field(const FieldCtx& f, size_t d, u64* g) {
   if (d > ((size_t)1 << 27)) return false;
   if (f.kind == F_GL) { *g = RONK_GOLDILOCKS_G; return true; }
   if (f.kind != F_MONT || ronk_check_prime(f.p) != RONK_OK) return false;
@@ -625,6 +625,22 @@ static bool newton_field(const FieldCtx& f, size_t d, u64* g) {
   if (h_powmod(z, (f.p - 1) / 2, f.p) != f.p - 1) return false;
   *g = z;
   return true;
+}
+
+// The Newton ladder of the series inverse: g (2 Lp words, g[0] = 1 / f[0] and ZERO above on entry) becomes 1 / f mod x^Lp for
+// f of Lp coefficients, Lp a power of two.  Scratch: e 4 Lp, h Lp, t1 2 Lp words.  Shared by the division below and by the
+// root of the multipoint walk (ronk_multipoint.hip).
+int newton_ladder_dev(const FieldCtx& fld, u64 G, const u64* f, size_t Lp, u64* g, u64* e, u64* h, u64* t1, hipStream_t s) {
+  const u64 P = fld.p;
+  for (size_t k = 1; k < Lp; k <<= 1) {
+    // e = f[0:2k] * g[0:k]: coefficients [k, 2k) are the error term (the low k are [1, 0, ..])
+    RCHK(ronk_poly_mul_dev(P, G, f, 2 * k, g, k, e, s));
+    FIELD_DISPATCH(fld, { hipLaunchKernelGGL((dv_neg_kernel<decltype(ops)>), dim3(grid_for(k)), dim3(256), 0, s, ops, e + k, h, k); });
+    // g[k:2k] = (g[0:k] * h)[0:k]
+    RCHK(ronk_poly_mul_dev(P, G, g, k, h, k, t1, s));
+    hipLaunchKernelGGL(dv_copy_kernel, dim3(grid_for(k)), dim3(256), 0, s, (const u64*)t1, k, g + k, k);
+  }
+  return RONK_OK;
 }
 
 // a: d coefficients with degree n (a[n] != 0), b: degree m (b[m] != 0), n >= m.  d_quot / d_rem: d coefficients each.
@@ -652,14 +668,7 @@ static int newton_divrem_dev(const FieldCtx& fld, u64 G, const u64* d_a, size_t 
   // g = 1 / f[0] = 1 / lead(b)   (precision 1)
   FIELD_DISPATCH(fld, { hipLaunchKernelGGL((dv_fill_inv_kernel<decltype(ops)>), dim3(grid_for(2 * Lp)), dim3(256), 0, s, ops, g.u(), 2 * Lp,
                                           d_b + m, d_a + n, full_status); });
-  for (size_t k = 1; k < Lp; k <<= 1) {
-    // e = f[0:2k] * g[0:k]: coefficients [k, 2k) are the error term (the low k are [1, 0, ..])
-    RCHK(ronk_poly_mul_dev(P, G, f.u(), 2 * k, g.u(), k, e.u(), s));
-    FIELD_DISPATCH(fld, { hipLaunchKernelGGL((dv_neg_kernel<decltype(ops)>), dim3(grid_for(k)), dim3(256), 0, s, ops, e.u() + k, h.u(), k); });
-    // g[k:2k] = (g[0:k] * h)[0:k]
-    RCHK(ronk_poly_mul_dev(P, G, g.u(), k, h.u(), k, t1.u(), s));
-    hipLaunchKernelGGL(dv_copy_kernel, dim3(grid_for(k)), dim3(256), 0, s, (const u64*)t1.u(), k, g.u() + k, k);
-  }
+  RCHK(newton_ladder_dev(fld, G, f.u(), Lp, g.u(), e.u(), h.u(), t1.u(), s));
   // qrev = (rev(a)[0:L] * g[0:L])[0:L]
   hipLaunchKernelGGL(dv_reverse_kernel, dim3(grid_for(L)), dim3(256), 0, s, d_a, n, ar.u(), L);
   RCHK(ronk_poly_mul_dev(P, G, ar.u(), L, g.u(), L, qr.u(), s));

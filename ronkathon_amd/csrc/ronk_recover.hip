@@ -4,11 +4,11 @@
 #include <map>
 
 #include "runtime.h"
-#include "roots_kernels.h"
+#include "roots_host.h"
 
 // ------------------------------------------------------------------------------------- kernels
 // the field a launch computes in: Goldilocks, or a Montgomery prime (its constants by value: SGPRs)
-static FieldConst roots_consts(u64 p) {
+FieldConst roots_consts(u64 p) {
   FieldConst c{};
   if (p == RONK_GOLDILOCKS_P) return c;
   const mont64::Field mf = mont64::make_field(p);
@@ -16,11 +16,6 @@ static FieldConst roots_consts(u64 p) {
   c.w16[0] = mf.one;
   return c;
 }
-#define ROOTS_DISPATCH(fc, ...)                        \
-  do {                                                 \
-    if ((fc).p == 0) { GlField f; __VA_ARGS__; }       \
-    else { MontField f(fc); __VA_ARGS__; }             \
-  } while (0)
 
 template <class FLD>
 __global__ void __launch_bounds__(256) roots_leaf_kernel(FieldConst fc, u64 p, const u64* __restrict__ roots, u64 m, u32 G,
@@ -36,6 +31,9 @@ __global__ void __launch_bounds__(256) roots_combine_kernel(FieldConst fc, const
   const u64 total = pairs * 2 * d;
   for (u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x; e < total; e += (u64)gridDim.x * blockDim.x)
     roots_combine_elem(f, prod, spread, pairs, d, st, e);
+}
+__global__ void __launch_bounds__(256) roots_single_leaf_kernel(const u64* __restrict__ leaf, u64 shift, u64 m, u64* __restrict__ out) {
+  roots_single_leaf_elem(leaf, shift, m, out, threadIdx.x);
 }
 struct DevAtom {
   __device__ u32 or32(u32* a, u32 v) const { return atomicOr(a, v); }
@@ -89,17 +87,7 @@ __global__ void __launch_bounds__(256) rec_finish_kernel(FieldConst fc, const u6
 // One batched plan per level shape (2d points, count / 2 rows), owned by the library: a second call of the same shape builds
 // no twiddle tables.  Every call holds g_roots_mu from its first lookup to its last launch, and pins what it uses; eviction
 // (least recently used, unpinned, beyond ROOTS_CACHE_MAX) waits for the entry's last work first.
-struct RootsPlan {
-  ronk_plan* pl = nullptr;
-  u64 p, g, batch;
-  u32 log2n;
-  int device;
-  hipEvent_t done = nullptr;
-  bool used = false;
-  u64 stamp = 0;
-  int pins = 0;
-};
-static std::mutex g_roots_mu;
+std::mutex g_roots_mu;
 static std::vector<RootsPlan*> g_roots_plans;
 static u64 g_roots_clock = 0;
 static const size_t ROOTS_CACHE_MAX = 48;
@@ -112,7 +100,7 @@ static void roots_plan_free(RootsPlan* e) {
 }
 // g_roots_mu held
 // tiled: the plan must run on the tile kernels (the tree's fused product, TileArgs::in2); otherwise RONK_ERR_UNSUPPORTED
-static int roots_plan_get(u64 p, u64 g, u32 log2n, u64 batch, bool tiled, RootsPlan** out) {
+int roots_plan_get(u64 p, u64 g, u32 log2n, u64 batch, bool tiled, RootsPlan** out) {
   int dev = 0;
   HIPCHK(hipGetDevice(&dev));
   for (RootsPlan* e : g_roots_plans)
@@ -147,29 +135,9 @@ static int roots_plan_get(u64 p, u64 g, u32 log2n, u64 batch, bool tiled, RootsP
   *out = e;
   return RONK_OK;
 }
-// the pins of one call: released (an event behind the call's work on `s`) when the call returns
-struct RootsPins {
-  std::vector<RootsPlan*> held;
-  hipStream_t s = nullptr;
-  ~RootsPins() {
-    for (RootsPlan* e : held) {
-      e->used = hipEventRecord(e->done, s) == hipSuccess;
-      if (!e->used) (void)hipGetLastError();
-      e->pins--;
-    }
-  }
-  int get(u64 p, u64 g, u32 log2n, u64 batch, bool tiled, ronk_plan** pl) {
-    RootsPlan* e = nullptr;
-    RCHK(roots_plan_get(p, g, log2n, batch, tiled, &e));
-    held.push_back(e);
-    *pl = e->pl;
-    return RONK_OK;
-  }
-};
-
 // leaf size G = 2^L.  L = 6 (64 factors per leaf): the first NTT level then has 2^7 points -- see DESIGN.md for the measurement of
 // L = 6 / 7 / 8.  RONK_ROOTS_LEAF_LOG2 (6 .. 8) overrides it for that A/B.
-static u32 roots_leaf() {
+u32 roots_leaf() {
   static const u32 G = [] {
     const char* e = getenv("RONK_ROOTS_LEAF_LOG2");
     const int l = e ? atoi(e) : 6;
@@ -190,46 +158,57 @@ static bool roots_tree_root(u64 p, u64* g) {
 }
 
 // words of workspace the tree of m roots needs: three spread arrays of 2M (M = m padded to G * 2^t); the roots sit in the second
-static size_t roots_padded(size_t m, u32 G) { size_t M = G; while (M < m) M <<= 1; return M; }
-static size_t roots_ws_words(size_t m, u32 G) { const size_t M = roots_padded(m, G); return M > G ? 6 * M : 3 * M; }
+size_t roots_padded(size_t m, u32 G) { size_t M = G; while (M < m) M <<= 1; return M; }
+size_t roots_ws_words(size_t m, u32 G) { const size_t M = roots_padded(m, G); return M > G ? 6 * M : 3 * M; }
 
 // prod_{i < m} (x - d_roots[i]) -> d_out[0 .. m] (monic, ascending).  ws: roots_ws_words(m) words.  g_roots_mu held.
-static int roots_tree(const FieldConst& fc, u64 p, u64 gtree, const u64* d_roots, size_t m, u64* d_out, u64* ws, RootsPins& pins,
-                      hipStream_t s) {
+// keep (may be NULL: nothing is retained, the tree of ronk_poly_from_roots): the leaves stay in keep->leaves (2M words, the
+// level-0 spread layout) and the forward transforms of level l (children of G * 2^l coefficients) in keep->transforms + l * 2M
+// (a rows, then b rows) -- what the walks of ronk_multipoint.hip read.  The products and launches are the same either way.
+int roots_tree(const FieldConst& fc, u64 p, u64 gtree, const u64* d_roots, size_t m, u64* d_out, u64* ws, RootsPins& pins,
+               hipStream_t s, const RootsKeep* keep) {
   const u32 G = roots_leaf();
   const size_t M = roots_padded(m, G);
   const size_t leaves = M / G;
-  u64* S = ws;                 // this level, spread
+  u64* S = keep ? keep->leaves : ws;   // this level, spread
   u64* T = ws + 2 * M;         // its transforms
   u64* S2 = ws + 4 * M;        // the next level, spread
   RootsStore st{};
-  if (leaves == 1) { st.out = d_out; st.final_ = 1; st.shift = M - m; st.m = m; }
+  if (leaves == 1 && !keep) { st.out = d_out; st.final_ = 1; st.shift = M - m; st.m = m; }
   else { st.out = S; st.half = M; }
   ROOTS_DISPATCH(fc, { hipLaunchKernelGGL((roots_leaf_kernel<decltype(f)>), dim3((u32)leaves), dim3(G), 0, s, fc, p, d_roots, (u64)m, G, st); });
   HIPCHK(hipGetLastError());
-  size_t d = G, count = leaves;
+  if (leaves == 1 && keep) {   // the single leaf is kept in the spread layout: its shifted copy is the product
+    hipLaunchKernelGGL(roots_single_leaf_kernel, dim3(1), dim3(G), 0, s, (const u64*)S, (u64)(M - m), (u64)m, d_out);
+    HIPCHK(hipGetLastError());
+  }
+  size_t d = G, count = leaves, level = 0;
   while (count > 1) {
     const size_t pairs = count / 2, half = pairs * 2 * d;
     ronk_plan* pl = nullptr;
     RCHK(pins.get(p, gtree, (u32)ilog2(2 * d), pairs, true, &pl));
-    RCHK(transform_dev(pl, false, S, nullptr, T, s));
-    RCHK(transform_dev(pl, false, S + half, nullptr, T + half, s));
-    RCHK(transform_dev(pl, true, T, T + half, T, s));     // a * b: the second half multiplied on load
+    u64* Tl = keep ? keep->transforms + level * 2 * M : T;
+    u64* prod = keep ? T : Tl;   // retained transforms are not overwritten by the product
+    RCHK(transform_dev(pl, false, S, nullptr, Tl, s));
+    RCHK(transform_dev(pl, false, S + half, nullptr, Tl + half, s));
+    RCHK(transform_dev(pl, true, Tl, Tl + half, prod, s));     // a * b: the second half multiplied on load
     RootsStore nx{};
     if (pairs == 1) { nx.out = d_out; nx.final_ = 1; nx.shift = M - m; nx.m = m; }
     else { nx.out = S2; nx.half = M; }
-    ROOTS_DISPATCH(fc, { hipLaunchKernelGGL((roots_combine_kernel<decltype(f)>), dim3(grid_for(half)), dim3(256), 0, s, fc, (const u64*)T,
+    ROOTS_DISPATCH(fc, { hipLaunchKernelGGL((roots_combine_kernel<decltype(f)>), dim3(grid_for(half)), dim3(256), 0, s, fc, (const u64*)prod,
                                             (const u64*)S, (u64)pairs, (u64)d, nx); });
     HIPCHK(hipGetLastError());
-    std::swap(S, S2);
+    if (keep && level == 0) { S = S2; S2 = ws; }   // the leaves stay where they are
+    else std::swap(S, S2);
     d *= 2;
     count = pairs;
+    level++;
   }
   return RONK_OK;
 }
 
 // which primes a tree of m roots serves: any odd prime up to one leaf, beyond that the 2-adicity of the top product (M points)
-static int roots_field(u64 p, size_t m, u64* gtree) {
+int roots_field(u64 p, size_t m, u64* gtree) {
   if (p < 3 || !(p & 1)) return p == 2 ? RONK_ERR_UNSUPPORTED : RONK_ERR_NOT_PRIME;
   RCHK(ronk_check_prime(p));
   const size_t M = roots_padded(m, roots_leaf());
@@ -240,7 +219,7 @@ static int roots_field(u64 p, size_t m, u64* gtree) {
   return RONK_OK;
 }
 
-static bool capturing(hipStream_t s) {
+bool roots_capturing(hipStream_t s) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
   return st != hipStreamCaptureStatusNone;
@@ -252,7 +231,7 @@ extern "C" int ronk_poly_from_roots_dev(uint64_t p, const uint64_t* d_roots, siz
   RCHK(roots_field(p, m ? m : 1, &gtree));
   RCHK(need_device());
   hipStream_t s = (hipStream_t)stream;
-  if (capturing(s)) return RONK_ERR_UNSUPPORTED;
+  if (roots_capturing(s)) return RONK_ERR_UNSUPPORTED;
   if (m == 0) {   // the empty product: ONE
     const u64 one = 1;
     HIPCHK(hipMemcpyAsync(d_out, &one, 8, hipMemcpyHostToDevice, s));
@@ -265,7 +244,7 @@ extern "C" int ronk_poly_from_roots_dev(uint64_t p, const uint64_t* d_roots, siz
   void* lease = nullptr;
   u64* ws = nullptr;
   RCHK(ws_lease_acquire(roots_ws_words(m, roots_leaf()) * 8, s, &lease, &ws));
-  const int rc = roots_tree(fc, p, gtree, d_roots, m, d_out, ws, pins, s);
+  const int rc = roots_tree(fc, p, gtree, d_roots, m, d_out, ws, pins, s, nullptr);
   ws_lease_release(lease);
   return rc;
 }
@@ -296,7 +275,7 @@ extern "C" int ronk_rs_recover_batch_dev(ronk_plan* plan, size_t k, const uint64
   if (k > N || n_erased > N - k) return RONK_ERR_INDEX;
   if (N < REC_CH || plan->field.kind == F_MOD2) return RONK_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (capturing(s)) return RONK_ERR_UNSUPPORTED;
+  if (roots_capturing(s)) return RONK_ERR_UNSUPPORTED;
   const size_t e = n_erased;
   u64 gtree = 0, sh = 1, sinv = 1, omega = 1;
   if (e) {
@@ -335,7 +314,7 @@ extern "C" int ronk_rs_recover_batch_dev(ronk_plan* plan, size_t k, const uint64
     ROOTS_DISPATCH(fc, { hipLaunchKernelGGL((rec_roots_kernel<decltype(f)>), dim3(grid_for(e)), dim3(256), 0, s, fc, d_erased, (u64)e, N,
                                             omega, bitmap, err, roots); });
     HIPCHK(hipGetLastError());
-    RCHK(roots_tree(fc, p, gtree, roots, e, zz, W, pins, s));
+    RCHK(roots_tree(fc, p, gtree, roots, e, zz, W, pins, s, nullptr));
     ronk_plan* pz = nullptr;
     RCHK(pins.get(p, plan->g % p, plan->log2n, 2, false, &pz));
     ROOTS_DISPATCH(fc, {

@@ -40,6 +40,12 @@ RONK_HD void roots_put(const RootsStore& s, u64 i, u64 d, u64 j, u64 v) {
   o[j + d] = 0;   // the zero half of a 2d-point row
 }
 
+// a tree that is ONE retained leaf (kept in the spread layout): element j of the leaf -> the caller's m + 1 coefficients
+RONK_HD void roots_single_leaf_elem(const u64* leaf, u64 shift, u64 m, u64* out, u64 j) {
+  if (j >= shift) out[j - shift] = leaf[j];
+  if (j == 0) out[m] = 1;
+}
+
 template <class FLD>
 RONK_HD u64 fld_pow(const FLD& f, u64 a, u64 e) {
   u64 r = 1;

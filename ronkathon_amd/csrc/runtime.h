@@ -4,6 +4,7 @@
 //   ronk_plan.hip     plans, transforms, plan cache, fft/ifft/dft, polynomial multiply, batched RS encode
 //   ronk_callers.hip  evaluate, division, Lagrange evaluate, Reed-Solomon encode/decode, KZG commit (MSM)
 //   ronk_dist.hip     multi-GPU four-step phases
+//   ronk_recover.hip  the product tree and erasure recovery;  ronk_multipoint.hip  multipoint evaluation / interpolation on it
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -39,6 +40,12 @@ int need_device();                              // RONK_OK or RONK_ERR_NO_DEVICE
 //      the work that uses it has been queued
 int ws_lease_acquire(size_t bytes, hipStream_t s, void** lease, u64** ptr);
 void ws_lease_release(void* lease);
+
+// ---- the Newton series inverse on the NTT path (ronk_callers.hip): which fields it serves for products of up to 2 * 2^ceil(log2 d)
+//      points (and with which transform root), and the ladder itself
+struct FieldCtx;
+bool newton_field(const FieldCtx& f, size_t d, u64* g);
+int newton_ladder_dev(const FieldCtx& fld, u64 G, const u64* f, size_t Lp, u64* g, u64* e, u64* h, u64* t1, hipStream_t s);
 
 // ---- host integer logic
 typedef unsigned __int128 u128;

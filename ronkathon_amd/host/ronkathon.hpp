@@ -261,6 +261,23 @@ template <class F> std::vector<F> poly_from_roots(const std::vector<F>& roots) {
   return out;
 }
 
+// f at every point of xs (Polynomial::evaluate in a loop, src/shamir/mod.rs:33-60) in one call (ronk_poly_eval_many)
+template <class F> std::vector<F> poly_eval_many(const std::vector<F>& coeffs, const std::vector<F>& xs) {
+  std::vector<F> out(xs.size());
+  check(ronk_poly_eval_many(F::ORDER, reinterpret_cast<const uint64_t*>(coeffs.data()), coeffs.size(),
+                            reinterpret_cast<const uint64_t*>(xs.data()), xs.size(), reinterpret_cast<uint64_t*>(out.data())));
+  return out;
+}
+// the xs.size() coefficients of the polynomial through (xs[i], ys[i]), any distinct nodes (ronk_poly_interpolate); coincident
+// nodes throw RONK_ERR_ZERO_INVERSE
+template <class F> std::vector<F> poly_interpolate(const std::vector<F>& xs, const std::vector<F>& ys) {
+  std::vector<F> out(xs.size());
+  check(xs.size() == ys.size() ? RONK_OK : RONK_ERR_INVALID);
+  check(ronk_poly_interpolate(F::ORDER, reinterpret_cast<const uint64_t*>(xs.data()), reinterpret_cast<const uint64_t*>(ys.data()),
+                              xs.size(), reinterpret_cast<uint64_t*>(out.data())));
+  return out;
+}
+
 // ---- KZG commit / open (src/kzg/setup.rs:45-78) over AffinePoint<PlutoExtendedCurve> (src/curve/mod.rs:66-73) --------
 struct AffinePoint {                       // Point(x, y) with x = x0 + x1 t, y = y0 + y1 t in GF(101^2), or Infinity
   std::array<uint64_t, 5> w{0, 0, 0, 0, 1};

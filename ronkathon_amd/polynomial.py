@@ -108,6 +108,16 @@ class Polynomial:
         return self.field(L.out_scalar(L.lib.ronk_lagrange_eval, self.field.ORDER, L.ptr(self.coefficients),
                                        L.ptr(self.basis.nodes), self.D, x))
 
+    def evaluate_many(self, xs):
+        """Monomial basis: the values at every point of `xs` (any points, repeats allowed) as a uint64 array, equal to
+        [self.evaluate(x) for x in xs], in one call (ronk_poly_eval_many)."""
+        self._mono()
+        x = L.arr([int(v) % self.field.ORDER for v in xs])
+        out = np.empty(x.size, dtype=np.uint64)
+        L.check(L.lib.ronk_poly_eval_many(self.field.ORDER, L.ptr(self.coefficients), self.D, L.ptr(x) if x.size else None, x.size,
+                                          L.ptr(out)))
+        return out
+
     # ---- arithmetic (arithmetic.rs)
     def _binary(self, fn, rhs):
         self._mono(); rhs._mono()
