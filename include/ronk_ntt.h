@@ -350,6 +350,47 @@ int ronk_kzg_open_bn254_dev(const uint64_t* d_coeffs, size_t n, const uint64_t z
 int ronk_kzg_open_bn254(const uint64_t* coeffs, size_t n, const uint64_t z[4], const uint64_t* srs, size_t n_srs,
                         uint64_t out_point[8], uint64_t out_value[4]);
 
+/* ---- NTT and polynomial product over the SCALAR field of BN254 (the field of ronk_kzg_open_bn254 above) ----
+ * The reference's Polynomial::{fft, ifft} (src/polynomial/mod.rs:240-323, :430-453) and Mul
+ * (src/polynomial/arithmetic.rs:97-119) are generic over F: FiniteField; these are their instances over Fr, what moves a
+ * polynomial that kzg::commit / kzg::open work on between coefficients and values on a power-of-two domain.
+ * Elements: 4 x 64-bit little-endian limbs, standard form, as everywhere above; inputs are any 256-bit integers, taken mod
+ * r, outputs canonical.  Natural order in and out.  omega_n = 5^((r-1)/n) (src/algebra/field/mod.rs:70-75: 5 generates
+ * Fr*, and r - 1 = 2^28 * odd, so n = 2^log2n with log2n <= 28; above that RONK_ERR_NO_ROOT, the reference's
+ * "n must divide p^q - 1").  The inverse uses omega^-1 and includes 1/n.  Kernels: csrc/fr_ntt_kernels.h (DESIGN.md "NTT
+ * over the BN254 scalar field").
+ *
+ * ronk_root_of_unity_bn254: omega_(2^log2n), host-side integer logic, no device work.
+ * ronk_plan_create_bn254: tables for one size (both directions).  A transform is 1 to 4 passes of at most 2^10 rows each;
+ * max_log2_tile (0 = default) caps the rows of every pass, so that a small transform can be made to take two or three
+ * passes (testing); RONK_ERR_UNSUPPORTED when the cap would need more than four.  ronk_plan_info_bn254 reports the passes
+ * and their log2 rows (entries past num_passes are 0).
+ * ronk_ntt_forward_bn254_dev / _inverse_: `batch` transforms of rows that are contiguous in d_in and d_out; they enqueue on
+ * `stream` and nothing else: no synchronisation, no allocation.  d_in == d_out is allowed.  Plans of two or more passes own
+ * a scratch of `reserved` x n elements, one row at creation; a batch above `reserved` runs as slices of `reserved` rows one
+ * behind the other.  ronk_plan_reserve_bn254 grows the scratch to `batch` rows so that such a batch runs as one set of
+ * launches: it allocates and synchronises the device (call it beside plan creation, not on a capturing stream).  The
+ * scratch is not guarded across streams: transforms that should overlap use one plan per stream.
+ * ronk_ntt_forward_bn254 / _inverse_: host buffers, one transform (plan, staging and synchronisation inside).
+ * ronk_poly_mul_bn254(_dev): exactly d + d2 - 1 coefficients (arithmetic.rs:97-119: the reference's product has D + D2 - 1)
+ * through an NTT of the next power of two >= d + d2 - 1; RONK_ERR_UNSUPPORTED when that exceeds 2^28.  The _dev form
+ * enqueues on `stream` and owns its scratch (the pooled workspace of ronk_poly_mul_dev, ronk_trim_workspace releases it);
+ * the twiddle tables of each NTT size a product has used (0.3 % of that size's data at 2^20, 27 MiB at 2^28) stay cached per
+ * device for the life of the process, outside that pool.  d_out may not overlap the operands.
+ * RONK_ERR_INVALID: NULL pointer, zero length or batch; RONK_ERR_NO_DEVICE without a GPU (after the argument checks). */
+int ronk_root_of_unity_bn254(uint32_t log2n, uint64_t out[4]);
+typedef struct ronk_fr_plan ronk_fr_plan;
+int ronk_plan_create_bn254(ronk_fr_plan** out, uint32_t log2n, uint32_t max_log2_tile);
+int ronk_plan_info_bn254(const ronk_fr_plan* plan, uint32_t* num_passes, uint32_t log2_rows[4]);
+int ronk_plan_reserve_bn254(ronk_fr_plan* plan, size_t batch);
+int ronk_plan_destroy_bn254(ronk_fr_plan* plan);
+int ronk_ntt_forward_bn254_dev(ronk_fr_plan* plan, const uint64_t* d_in, uint64_t* d_out, size_t batch, void* stream);
+int ronk_ntt_inverse_bn254_dev(ronk_fr_plan* plan, const uint64_t* d_in, uint64_t* d_out, size_t batch, void* stream);
+int ronk_ntt_forward_bn254(uint32_t log2n, const uint64_t* in, uint64_t* out);
+int ronk_ntt_inverse_bn254(uint32_t log2n, const uint64_t* in, uint64_t* out);
+int ronk_poly_mul_bn254_dev(const uint64_t* d_a, size_t d, const uint64_t* d_b, size_t d2, uint64_t* d_out, void* stream);
+int ronk_poly_mul_bn254(const uint64_t* a, size_t d, const uint64_t* b, size_t d2, uint64_t* out);
+
 /* ---- multi-GPU four-step building blocks (one process per GPU; the exchange between the two
  *      phases is an RCCL all-to-all issued by the host side, see ronkathon_amd/dist.py) ----
  * n = 2^log2n split as R x C with R = 2^(log2n - log2n/2) rows and C = 2^(log2n/2) columns;

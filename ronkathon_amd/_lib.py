@@ -118,6 +118,17 @@ _SIG = {
     "ronk_poly_div_linear_bn254_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "ronk_kzg_open_bn254_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ronk_kzg_open_bn254": (_int, [_vp, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "ronk_root_of_unity_bn254": (_int, [C.c_uint32, _vp]),
+    "ronk_plan_create_bn254": (_int, [C.POINTER(_vp), C.c_uint32, C.c_uint32]),
+    "ronk_plan_info_bn254": (_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "ronk_plan_reserve_bn254": (_int, [_vp, _sz]),
+    "ronk_plan_destroy_bn254": (_int, [_vp]),
+    "ronk_ntt_forward_bn254_dev": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "ronk_ntt_inverse_bn254_dev": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "ronk_ntt_forward_bn254": (_int, [C.c_uint32, _vp, _vp]),
+    "ronk_ntt_inverse_bn254": (_int, [C.c_uint32, _vp, _vp]),
+    "ronk_poly_mul_bn254_dev": (_int, [_vp, _sz, _vp, _sz, _vp, _vp]),
+    "ronk_poly_mul_bn254": (_int, [_vp, _sz, _vp, _sz, _vp]),
     "ronk_dist_plan_create": (_int, [C.POINTER(_vp), C.c_uint32, _int, _int, _int, _int]),
     "ronk_dist_plan_destroy": (_int, [_vp]),
     "ronk_dist_plan_create_chunked": (_int, [C.POINTER(_vp), C.c_uint32, _int, _int, _int, _int, _int]),
@@ -471,3 +482,40 @@ class ShardedMulPlan:
     def __del__(self):
         if lib is not None:
             self.close()
+
+
+class FrPlan:
+    """ronk_fr_plan (include/ronk_ntt.h): a transform of 2^log2n elements of BN254's scalar field, 4 words each.
+    max_log2_tile caps the rows of every pass (0: the default plan)."""
+
+    def __init__(self, log2n, max_log2_tile=0):
+        self.h = _vp()
+        self.log2n = log2n
+        check(lib.ronk_plan_create_bn254(C.byref(self.h), log2n, max_log2_tile))
+
+    def info(self):
+        """-> the log2 rows of every pass, in order"""
+        n, rows = C.c_uint32(0), (C.c_uint32 * 4)()
+        check(lib.ronk_plan_info_bn254(self.h, C.byref(n), rows))
+        return [int(rows[i]) for i in range(n.value)]
+
+    def reserve(self, batch):
+        """scratch for `batch` rows per set of launches (allocates and synchronises; a larger batch still runs, in slices)"""
+        check(lib.ronk_plan_reserve_bn254(self.h, batch))
+
+    def forward_dev(self, d_in, d_out, batch=1, stream=None):
+        check(lib.ronk_ntt_forward_bn254_dev(self.h, d_in, d_out, batch, stream))
+
+    def inverse_dev(self, d_in, d_out, batch=1, stream=None):
+        check(lib.ronk_ntt_inverse_bn254_dev(self.h, d_in, d_out, batch, stream))
+
+    def close(self):
+        if self.h:
+            lib.ronk_plan_destroy_bn254(self.h)
+            self.h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -189,6 +189,57 @@ class Poseidon:
         return [int(v) for v in self.handle.hash_state(values)]
 
 
+def _words4(values):
+    """integers < 2^256 -> n x 4 words, little endian"""
+    buf = b"".join(int(v).to_bytes(32, "little") for v in values)
+    return np.frombuffer(buf, dtype=np.uint64).reshape(-1, 4).copy()
+
+
+def _ints4(words):
+    buf = np.ascontiguousarray(words, dtype=np.uint64).tobytes()
+    return [int.from_bytes(buf[i:i + 32], "little") for i in range(0, len(buf), 32)]
+
+
+def _transform_bn254(fn, values):
+    n = len(values)
+    if n == 0 or n & (n - 1):
+        raise L.RonkPanic(L.ERR_NOT_POW2)
+    x = _words4(values)
+    out = np.zeros_like(x)
+    L.check(fn(n.bit_length() - 1, L.ptr(x), L.ptr(out)))
+    return _ints4(out)
+
+
+def ntt_bn254(values):
+    """`Polynomial::fft` (polynomial/mod.rs:240-323) over BN254's scalar field: the values of the polynomial with these
+    coefficients (integers < 2^256, taken mod r) at omega^0 .. omega^(n-1), omega = 5^((r-1)/n), n = len(values) a power of two."""
+    return _transform_bn254(L.lib.ronk_ntt_forward_bn254, values)
+
+
+def intt_bn254(values):
+    """`Polynomial::ifft` (polynomial/mod.rs:430-453) over BN254's scalar field: coefficients from the values on the domain"""
+    return _transform_bn254(L.lib.ronk_ntt_inverse_bn254, values)
+
+
+def poly_mul_bn254(a, b):
+    """`Polynomial * Polynomial` (polynomial/arithmetic.rs:97-119) over BN254's scalar field: the len(a) + len(b) - 1
+    coefficients of the product (integers, taken mod r)"""
+    if not len(a) or not len(b):
+        raise L.RonkPanic(L.ERR_INVALID)
+    aw, bw = _words4(a), _words4(b)
+    out = np.zeros((len(a) + len(b) - 1, 4), dtype=np.uint64)
+    L.check(L.lib.ronk_poly_mul_bn254(L.ptr(aw), len(a), L.ptr(bw), len(b), L.ptr(out)))
+    return _ints4(out)
+
+
+def kzg_commit_evals_bn254(evals, srs):
+    """`kzg::commit` (kzg/setup.rs:45-60) of a polynomial held as its values on the domain of len(evals) points: the inverse
+    transform, then msm_bn254 of the coefficients against `srs`"""
+    if len(srs) < len(evals):
+        raise L.RonkPanic(L.ERR_INDEX)      # assert!(g1_srs.len() >= coeffs.len()), kzg/setup.rs:53
+    return msm_bn254(list(srs[:len(evals)]), intt_bn254(evals))
+
+
 def _dev_copy(a):
     """host array -> a fresh device buffer (freed by the caller with ronk_dev_free)"""
     d = C.c_void_p()
