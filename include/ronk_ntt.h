@@ -599,6 +599,63 @@ int ronk_merkle_open(const uint64_t* tree, size_t n_leaves, size_t digest_len, c
 int ronk_merkle_verify(const ronk_poseidon* h, const uint64_t* leaves, size_t n_idx, size_t leaf_len, const uint64_t* indices,
                        const uint64_t* paths, size_t n_leaves, size_t digest_len, const uint64_t* root, int* ok);
 
+/* ---- FRI over the 64-bit fields: the split-and-fold commit phase, Fiat-Shamir challenges from the caller's Poseidon handle,
+ *      the query phase and the verifier, for ONE codeword that is already in device memory (what ronk_lde_batch_dev leaves
+ *      behind).  The reference has no FRI; the semantics are fixed here and restated on Python integers in tests/fri_ref.py.
+ *        field     that of the Poseidon handle: Goldilocks or any odd prime p < 2^64 with 2^log2_n | p - 1.
+ *        domain    x_i = s w^i, i < N_0 = 2^log2_n, natural order, w = ronk_root_of_unity(p, g, N_0), s = coset_shift != 0;
+ *                  layer 0 is the N_0 words f_0[i] = f(x_i).
+ *        fold      f'[i] = (a + b) / 2 + beta (a - b) / (2 x_i) with a = f[i], b = f[i + N/2], i < N/2; the new domain is
+ *                  s^2 <w^2>.  A layer of arity A = 2^log2_arity (2, 4 or 8) is log2_arity such folds with the challenges beta,
+ *                  beta^2, beta^4: in coefficients g_k = sum_(j < A) beta^j c_(A k + j).  Output i < N/A reads only the coset
+ *                  f[i + t N/A], t < A, which is Merkle leaf i of the layer (leaf_len = A, item_stride = 1, elem_stride = N/A in
+ *                  the addressing of ronk_merkle_commit_dev).
+ *        layers    L = (log2_n - log2_final) / log2_arity >= 1 (a remainder: RONK_ERR_INVALID), N_l = N_0 / A^l; layers
+ *                  0 .. L - 1 are committed -- layer 0 by this call -- and layer L, 2^log2_final words, is sent in the clear.
+ *        transcript  one-shot sponges of the handle, D = digest_len <= rate:  c_0 = seed (D words);  t_l = sponge(c_l || root_l)
+ *                  squeezing D words, beta_l = t_l[0], c_(l+1) = t_l;  u = sponge(c_L || final layer) squeezing D words;  query q
+ *                  has j_0 = sponge(u || [q])[0] & (N_0 / A - 1).  Repeated indices are allowed, and the bias of reducing a
+ *                  sponge word below p before masking is ignored.
+ *        queries   at layer l the leaf j_l = j_0 mod (N_l / A) is opened: its A values and log2(N_l / A) sibling digests.  Its
+ *                  fold must equal slot j_l div (N_(l+1) / A) of the leaf opened at layer l + 1, and final[j_(L-1)] at the end.
+ *        final     the interpolant of the final layer on s^(A^L) <w_(N_L)> has zero coefficients from N_L >> log2_blowup on
+ *                  (log2_blowup <= log2_final <= 8).
+ *        proof     canonical words: [L][D] roots, [N_L] final, then per layer l < L: [Q][A] leaf values, [Q][depth_l][D] paths.
+ *                  Indices are not stored.
+ *      Parameters and soundness are the caller's concern: the challenge is a BASE-field element, and the query count, the
+ *      blowup and the Poseidon constants decide what a proof is worth.  Batched or DEEP composition of several columns is out
+ *      of scope: one column per call. */
+typedef struct ronk_fri ronk_fri;
+/* The argument checks of ronk_fri_create, host-side integer logic (p, rate: the Poseidon handle's): 2^log2_n does not divide
+ * p - 1: RONK_ERR_NO_ROOT; log2_final > 8 or n_queries > 2^16: RONK_ERR_UNSUPPORTED; coset_shift = 0 (mod p), log2_arity outside
+ * 1 .. 3, log2_blowup > log2_final, log2_n < log2_final + log2_arity or a remainder in the layer count, n_queries = 0, digest_len
+ * = 0 or > rate, g without the full power-of-two order: RONK_ERR_INVALID. */
+int ronk_fri_check(uint64_t p, uint32_t rate, uint64_t g, uint32_t log2_n, uint64_t coset_shift, uint32_t log2_arity,
+                   uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len);
+/* Sizes in words, 0 for sizes ronk_fri_check refuses.  Proof: as laid out above.  Workspace: the folded layers 1 .. L, the trees of
+ * layers 0 .. L - 1 and L + (L + 2) D + L Q + Q words of transcript and query state. */
+size_t ronk_fri_proof_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len);
+size_t ronk_fri_workspace_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len);
+/* The handle keeps the inverse-point tables of every layer and the verifier's state on the current device; it borrows `pos`,
+ * which must outlive it.  Arguments are checked (ronk_fri_check) before a device is needed.  One verify call at a time per handle. */
+int ronk_fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint32_t log2_n, uint64_t coset_shift, uint32_t log2_arity,
+                    uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len);
+int ronk_fri_destroy(ronk_fri* fri);
+/* One layer as a building block: d_in is layer `layer` (N_l words, any 64-bit values), *d_beta the challenge in device memory,
+ * d_out receives N_l / A canonical words and must not overlap d_in.  Asynchronous. */
+int ronk_fri_fold_dev(const ronk_fri* fri, uint32_t layer, const uint64_t* d_in, const uint64_t* d_beta, uint64_t* d_out, void* stream);
+/* d_evals: layer 0; d_seed: D words; d_work: ronk_fri_workspace_words words and d_proof: ronk_fri_proof_words words, both
+ * caller-owned.  Asynchronous on `stream` with no host round trip (the challenges stay in device memory); it uses no library
+ * workspace.  Commits through ronk_merkle_commit_dev and opens through ronk_merkle_open_dev. */
+int ronk_fri_prove_dev(const ronk_fri* fri, const uint64_t* d_evals, const uint64_t* d_seed, uint64_t* d_work, uint64_t* d_proof,
+                       void* stream);
+/* *d_status (written by the call) = 0, or a set of bits: 1 a Merkle path fails (checked by ronk_merkle_verify_dev), 2 a fold
+ * mismatch, 4 the final layer is not of low degree.  Every check runs whatever the others find.  Asynchronous. */
+int ronk_fri_verify_dev(const ronk_fri* fri, const uint64_t* d_proof, const uint64_t* d_seed, int* d_status, void* stream);
+/* Host-pointer forms, synchronous. */
+int ronk_fri_prove(const ronk_fri* fri, const uint64_t* evals, const uint64_t* seed, uint64_t* proof);
+int ronk_fri_verify(const ronk_fri* fri, const uint64_t* proof, const uint64_t* seed, int* status);
+
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);
 int ronk_dev_free(void* ptr);

@@ -176,6 +176,16 @@ _SIG = {
     "ronk_merkle_commit": (_int, [_vp, _vp, _sz, _sz, _sz, _vp]),
     "ronk_merkle_open": (_int, [_vp, _sz, _sz, _vp, _sz, _vp, _vp]),
     "ronk_merkle_verify": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _vp, _vp]),
+    "ronk_fri_check": (_int, [_u64, C.c_uint32, _u64, C.c_uint32, _u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "ronk_fri_proof_words": (_sz, [C.c_uint32] * 5),
+    "ronk_fri_workspace_words": (_sz, [C.c_uint32] * 5),
+    "ronk_fri_create": (_int, [C.POINTER(_vp), _vp, _u64, C.c_uint32, _u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "ronk_fri_destroy": (_int, [_vp]),
+    "ronk_fri_fold_dev": (_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "ronk_fri_prove_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "ronk_fri_verify_dev": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ronk_fri_prove": (_int, [_vp, _vp, _vp, _vp]),
+    "ronk_fri_verify": (_int, [_vp, _vp, _vp, C.POINTER(_int)]),
     "ronk_dev_alloc": (_int, [C.POINTER(_vp), _sz]),
     "ronk_dev_free": (_int, [_vp]),
     "ronk_memcpy_h2d": (_int, [_vp, _vp, _sz]),
@@ -362,6 +372,54 @@ def merkle_level_offset(n_leaves, digest_len, level):
 
 def merkle_open_dev(d_tree, n_leaves, digest_len, d_indices, n_idx, d_paths, d_status, stream=0):
     check(lib.ronk_merkle_open_dev(d_tree, n_leaves, digest_len, d_indices, n_idx, d_paths, d_status, stream))
+
+
+class FriHandle:
+    """ronk_fri: one FRI instance (log2_n, coset shift, arity, final size, blowup, queries, digest length) on a PoseidonHandle,
+    which it borrows.  The _dev methods take raw device pointers (int) and enqueue on `stream`."""
+
+    def __init__(self, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len):
+        self.h = _vp()
+        self.pos = pos      # keeps the Poseidon handle alive
+        check(lib.ronk_fri_create(C.byref(self.h), pos.h, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries,
+                                  digest_len))
+        self.shape = (log2_n, log2_arity, log2_final, n_queries, digest_len)
+        self.n, self.arity, self.digest_len = 1 << log2_n, 1 << log2_arity, digest_len
+        self.proof_words = lib.ronk_fri_proof_words(*self.shape)
+        self.workspace_words = lib.ronk_fri_workspace_words(*self.shape)
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib.ronk_fri_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def fold_dev(self, layer, d_in, d_beta, d_out, stream=0):
+        check(lib.ronk_fri_fold_dev(self.h, layer, d_in, d_beta, d_out, stream))
+
+    def prove_dev(self, d_evals, d_seed, d_work, d_proof, stream=0):
+        check(lib.ronk_fri_prove_dev(self.h, d_evals, d_seed, d_work, d_proof, stream))
+
+    def verify_dev(self, d_proof, d_seed, d_status, stream=0):
+        check(lib.ronk_fri_verify_dev(self.h, d_proof, d_seed, d_status, stream))
+
+    def prove(self, evals, seed):
+        evals, seed = arr(evals), arr(seed)
+        if evals.size != self.n or seed.size != self.digest_len:
+            raise RonkPanic(ERR_INVALID, "evals holds 2^log2_n words, seed digest_len")
+        proof = np.empty(self.proof_words, dtype=np.uint64)
+        check(lib.ronk_fri_prove(self.h, ptr(evals), ptr(seed), ptr(proof)))
+        return proof
+
+    def verify(self, proof, seed):
+        proof, seed = arr(proof), arr(seed)
+        if proof.size != self.proof_words or seed.size != self.digest_len:
+            raise RonkPanic(ERR_INVALID, "proof holds ronk_fri_proof_words words, seed digest_len")
+        st = _int(-1)
+        check(lib.ronk_fri_verify(self.h, ptr(proof), ptr(seed), C.byref(st)))
+        return st.value
 
 
 class ShardedPlan:

@@ -334,3 +334,49 @@ class MerkleTree:
         L.check(L.lib.ronk_merkle_verify(self.handle.h, L.ptr(lv), 1, lv.size, L.ptr(idx), L.ptr(path), self.n, self.digest_len,
                                          L.ptr(root), ok))
         return bool(ok[0])
+
+
+class Fri:
+    """The FRI prover and verifier of include/ronk_ntt.h ("FRI") for one column over a 64-bit field: `evals` are the values of a
+    polynomial on the coset coset_shift * <omega_N>, N = 2^log2_n, natural order.  sponge_params as for MerkleTree.  Parameters
+    and soundness (a base-field challenge, the query count, the Poseidon constants) are the caller's concern."""
+
+    def __init__(self, sponge_params, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, g=None):
+        field = sponge_params[0]
+        self.field = field
+        self.poseidon = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
+        self.handle = L.FriHandle(self.poseidon, field._G if g is None else g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup,
+                                  n_queries, digest_len)
+        self.log2_n, self.log2_arity = log2_n, log2_arity
+
+    def prove(self, evals, seed):
+        """-> the proof, ronk_fri_proof_words canonical words"""
+        return self.handle.prove(evals, seed)
+
+    def verify(self, proof, seed):
+        """-> 0, or bits: 1 a Merkle path fails, 2 a fold mismatch, 4 the final layer is not of low degree"""
+        return self.handle.verify(proof, seed)
+
+    def fold(self, values, beta, layer=0):
+        """one layer of arity 2^log2_arity: N_layer words -> N_layer / arity canonical words"""
+        v = L.arr(values)
+        n_in = 1 << (self.log2_n - self.log2_arity * layer)
+        if v.size != n_in:
+            raise L.RonkPanic(L.ERR_INVALID, "layer %d holds %d words" % (layer, n_in))
+        n_out = n_in >> self.log2_arity
+        b = L.arr([int(beta)])
+        out = np.empty(n_out, dtype=np.uint64)
+        bufs = [C.c_void_p() for _ in range(3)]
+        try:
+            for buf, words in zip(bufs, (n_in, 1, n_out)):
+                L.check(L.lib.ronk_dev_alloc(C.byref(buf), words * 8))
+            L.check(L.lib.ronk_memcpy_h2d(bufs[0], L.ptr(v), n_in * 8))
+            L.check(L.lib.ronk_memcpy_h2d(bufs[1], L.ptr(b), 8))
+            self.handle.fold_dev(layer, bufs[0], bufs[1], bufs[2])
+            L.check(L.lib.ronk_dev_sync())
+            L.check(L.lib.ronk_memcpy_d2h(L.ptr(out), bufs[2], n_out * 8))
+        finally:
+            for buf in bufs:
+                if buf:
+                    L.lib.ronk_dev_free(buf)
+        return out

@@ -1,0 +1,328 @@
+// ronk_fri.hip -- C ABI of libronk_ntt.so, part 9: the FRI prover and verifier over the 64-bit fields, on the Poseidon sponge
+// and Merkle commitment of ronk_hash.hip (csrc/fri_kernels.h).
+#include "runtime.h"
+#include "hip_launch.h"
+#include "poseidon_handle.h"
+#include "fri_kernels.h"
+
+// ------------------------------------------------------------------------------------- handle
+struct ronk_fri {
+  const ronk_poseidon* pos;
+  u64 p, g, shift;
+  FriShape sh;
+  u32 log2_blowup;
+  bool mont;                    // Montgomery policy (any prime, and Goldilocks under a root convention without shift roots)
+  FriConsts k;
+  std::vector<FriLayer> layers;   // host copy; the table pointers are device pointers
+  u64* d_tab = nullptr;         // per layer lo, hi; then the final layer's w^-j
+  const u64* d_wfin = nullptr;
+  FriLayer* d_layers = nullptr;
+  u64* d_vs = nullptr;          // the verifier's state: the small words of FriShape, then ok [L][Q] ints
+};
+
+// the small state inside a workspace
+struct FriSmall {
+  u64 *betas, *chain, *u, *idx;
+  int* st;
+  FriSmall(const FriShape& sh, u64* base) {
+    betas = base;
+    chain = betas + sh.layers;
+    u = chain + (sh.layers + 1) * sh.d;
+    idx = u + sh.d;
+    st = (int*)(idx + sh.layers * sh.queries);
+  }
+};
+
+#define FRI_DISPATCH_E(F, eta, ...)                                       \
+  do {                                                                    \
+    if ((eta) == 1) { constexpr int ETA = 1; typedef F FF; __VA_ARGS__; } \
+    else if ((eta) == 2) { constexpr int ETA = 2; typedef F FF; __VA_ARGS__; } \
+    else { constexpr int ETA = 3; typedef F FF; __VA_ARGS__; }            \
+  } while (0)
+// run the statement with FF and ETA bound to the handle's field policy and arity
+#define FRI_DISPATCH(h, ...)                                        \
+  do {                                                              \
+    if ((h)->mont) FRI_DISPATCH_E(FriMont, (h)->sh.eta, __VA_ARGS__); \
+    else FRI_DISPATCH_E(FriGl, (h)->sh.eta, __VA_ARGS__);           \
+  } while (0)
+
+// ------------------------------------------------------------------------------------- kernels
+// one lane per output: A loads at stride m (coalesced across lanes), one store
+template <class F, int ETA>
+__global__ void __launch_bounds__(256) fri_fold_kernel(FriConsts k, FriLayer ly, const u64* __restrict__ in, const u64* __restrict__ beta,
+                                                       u64* __restrict__ out) {
+  const F f(k);
+  const u64 m = (u64)1 << ly.log2m;
+  const u64 b = f.in(*beta);
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < m; i += (u64)gridDim.x * blockDim.x)
+    out[i] = fri_fold_leaf<F, ETA>(f, fri_gamma(f, ly, i, b), [&](int t) { return in[i + (u64)t * m]; });
+}
+
+template <class PF, int W>
+__global__ void __launch_bounds__(64) fri_transcript_kernel(PoseidonConsts k, u32 d, const u64* seed, u64* chain, const u64* roots, u32 l0,
+                                                            u32 l1, u64* betas, const u64* fin, u64 nl, u64* u) {
+  if (blockIdx.x || threadIdx.x) return;
+  const PF pf(k);
+  fri_transcript<PF, W>(pf, k, d, seed, chain, roots, l0, l1, betas, fin, nl, u);
+}
+
+template <class PF, int W>
+__global__ void __launch_bounds__(256) fri_index_kernel(PoseidonConsts k, u32 d, const u64* __restrict__ u, const FriLayer* __restrict__ layers,
+                                                        u32 n_layers, u64 n_queries, u64* __restrict__ idx) {
+  const PF pf(k);
+  for (u64 q = blockIdx.x * (u64)blockDim.x + threadIdx.x; q < n_queries; q += (u64)gridDim.x * blockDim.x)
+    fri_query_indices<PF, W>(pf, k, d, u, layers, n_layers, n_queries, q, idx);
+}
+
+// the opened leaves of one layer, canonical: out[q][t] = vals[idx[q] + t m]
+template <class F>
+__global__ void __launch_bounds__(256) fri_gather_kernel(FriConsts k, const u64* __restrict__ vals, u32 log2m, u32 eta,
+                                                         const u64* __restrict__ idx, u64 n_queries, u64* __restrict__ out) {
+  const F f(k);
+  const u64 total = n_queries << eta;
+  for (u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x; e < total; e += (u64)gridDim.x * blockDim.x) {
+    const u64 q = e >> eta, t = e & (((u64)1 << eta) - 1);
+    out[e] = f.out(f.in(vals[idx[q] + (t << log2m)]));
+  }
+}
+
+// one lane per query: the Merkle flags of its layers (bit 1) and the fold consistency (bit 2)
+template <class F, int ETA>
+__global__ void __launch_bounds__(256) fri_check_kernel(FriConsts k, const FriLayer* __restrict__ layers, u32 n_layers, u64 n_queries,
+                                                        const u64* __restrict__ proof, u64 final_off, const u64* __restrict__ betas,
+                                                        const u64* __restrict__ idx, const int* __restrict__ ok, int* status) {
+  const F f(k);
+  for (u64 q = blockIdx.x * (u64)blockDim.x + threadIdx.x; q < n_queries; q += (u64)gridDim.x * blockDim.x) {
+    int bits = 0;
+    for (u32 l = 0; l < n_layers; l++)
+      if (!ok[(u64)l * n_queries + q]) bits |= 1;
+    if (!fri_check_query<F, ETA>(f, layers, n_layers, n_queries, proof, final_off, betas, idx, q)) bits |= 2;
+    if (bits) atomicOr(status, bits);
+  }
+}
+
+// one workgroup: lane k holds coefficient k of the final layer's interpolant; those from `first` on must vanish (bit 4)
+template <class F>
+__global__ void __launch_bounds__(256) fri_final_kernel(FriConsts k, const u64* __restrict__ wtab, const u64* __restrict__ fin, u32 n,
+                                                        u32 first, int* status) {
+  const F f(k);
+  const u32 c = threadIdx.x;
+  if (c >= first && c < n && fri_final_coeff(f, wtab, fin, n, c) != 0) atomicOr(status, 4);
+}
+
+// ------------------------------------------------------------------------------------- arguments and sizes
+extern "C" int ronk_fri_check(uint64_t p, uint32_t rate, uint64_t g, uint32_t log2_n, uint64_t coset_shift, uint32_t log2_arity,
+                              uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len) {
+  if (p < 3 || !(p & 1)) return RONK_ERR_INVALID;
+  if (log2_arity < 1 || log2_arity > 3) return RONK_ERR_INVALID;
+  if (log2_final > 8) return RONK_ERR_UNSUPPORTED;
+  if (log2_blowup > log2_final) return RONK_ERR_INVALID;
+  if (log2_n > 63 || ((p - 1) & (((u64)1 << log2_n) - 1))) return RONK_ERR_NO_ROOT;
+  if (log2_n < log2_final + log2_arity || (log2_n - log2_final) % log2_arity) return RONK_ERR_INVALID;
+  if (!n_queries || !digest_len || digest_len > rate) return RONK_ERR_INVALID;
+  if (n_queries > (1u << 16)) return RONK_ERR_UNSUPPORTED;
+  if (coset_shift % p == 0 || g % p == 0) return RONK_ERR_INVALID;
+  // w_N = g^((p - 1) / N) must have order N exactly (g a generator, or at least of full 2-power order)
+  if (fri_powmod(g, (p - 1) >> 1, p) == 1) return RONK_ERR_INVALID;
+  return RONK_OK;
+}
+
+static bool fri_shape(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len, FriShape* sh) {
+  if (log2_arity < 1 || log2_arity > 3 || log2_final > 8 || log2_n > 63 || log2_n < log2_final + log2_arity ||
+      (log2_n - log2_final) % log2_arity || !n_queries || !digest_len)
+    return false;
+  sh->n = log2_n; sh->eta = log2_arity; sh->log2_final = log2_final; sh->layers = (log2_n - log2_final) / log2_arity;
+  sh->queries = n_queries; sh->d = digest_len;
+  return true;
+}
+extern "C" size_t ronk_fri_proof_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len) {
+  FriShape sh;
+  return fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &sh) ? (size_t)sh.proof_words() : 0;
+}
+extern "C" size_t ronk_fri_workspace_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries,
+                                           uint32_t digest_len) {
+  FriShape sh;
+  return fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &sh) ? (size_t)sh.workspace_words() : 0;
+}
+
+// ------------------------------------------------------------------------------------- handle
+extern "C" int ronk_fri_destroy(ronk_fri* h) {
+  if (!h) return RONK_ERR_INVALID;
+  if (h->d_tab) (void)hipFree(h->d_tab);
+  if (h->d_layers) (void)hipFree(h->d_layers);
+  if (h->d_vs) (void)hipFree(h->d_vs);
+  delete h;
+  return RONK_OK;
+}
+
+extern "C" int ronk_fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint32_t log2_n, uint64_t coset_shift,
+                               uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len) {
+  if (!out) return RONK_ERR_INVALID;
+  *out = nullptr;
+  if (!pos) return RONK_ERR_INVALID;
+  RCHK(ronk_fri_check(pos->p, pos->rate, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len));
+  RCHK(need_device());
+  ronk_fri* h = new ronk_fri;
+  h->pos = pos; h->p = pos->p; h->g = g % h->p; h->shift = coset_shift % h->p; h->log2_blowup = log2_blowup;
+  fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &h->sh);
+  const FriShape& sh = h->sh;
+  h->mont = !fri_gl_shift_roots(h->p, h->g, sh.eta);
+  h->k = fri_host_consts(h->mont, h->p, h->g, sh.eta);
+  // tables: per layer lo then hi, then the final layer's roots
+  std::vector<size_t> off(sh.layers + 1);
+  size_t words = 0;
+  for (u32 l = 0; l < sh.layers; l++) {
+    const u32 lm = sh.log2m(l), kb = fri_kbits(lm);
+    off[l] = words;
+    words += ((size_t)1 << kb) + ((size_t)1 << (lm - kb));
+  }
+  off[sh.layers] = words;
+  words += (size_t)sh.size(sh.layers);
+  std::vector<u64> tab(words);
+  for (u32 l = 0; l < sh.layers; l++) {
+    const u32 kb = fri_kbits(sh.log2m(l));
+    fri_host_layer_table(h->mont, h->p, h->g, h->shift, sh, l, tab.data() + off[l], tab.data() + off[l] + ((size_t)1 << kb));
+  }
+  fri_host_final_table(h->mont, h->p, h->g, sh, tab.data() + off[sh.layers]);
+  int rc = upload(tab, &h->d_tab);
+  if (rc != RONK_OK) { ronk_fri_destroy(h); return rc; }
+  h->d_wfin = h->d_tab + off[sh.layers];
+  h->layers.resize(sh.layers);
+  for (u32 l = 0; l < sh.layers; l++) {
+    FriLayer& ly = h->layers[l];
+    ly.log2m = sh.log2m(l); ly.kbits = fri_kbits(ly.log2m);
+    ly.lo = h->d_tab + off[l]; ly.hi = ly.lo + ((size_t)1 << ly.kbits);
+    ly.leaf_off = sh.leaf_off(l); ly.path_off = sh.path_off(l);
+  }
+  hipError_t e = hipMalloc((void**)&h->d_layers, sh.layers * sizeof(FriLayer));
+  if (e == hipSuccess) e = hipMemcpy(h->d_layers, h->layers.data(), sh.layers * sizeof(FriLayer), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void**)&h->d_vs, (sh.small_words() + sh.layers * sh.queries) * 8);
+  if (e != hipSuccess) { ronk_fri_destroy(h); return hip_fail(e, "ronk_fri_create"); }
+  *out = h;
+  return RONK_OK;
+}
+
+// ------------------------------------------------------------------------------------- device entry points
+extern "C" int ronk_fri_fold_dev(const ronk_fri* h, uint32_t layer, const uint64_t* d_in, const uint64_t* d_beta, uint64_t* d_out,
+                                 void* stream) {
+  if (!h || !d_in || !d_beta || !d_out || layer >= h->sh.layers) return RONK_ERR_INVALID;
+  const FriLayer& ly = h->layers[layer];
+  FRI_DISPATCH(h, hipLaunchKernelGGL((fri_fold_kernel<FF, ETA>), dim3(grid_for((size_t)1 << ly.log2m)), dim3(256), 0, (hipStream_t)stream,
+                                     h->k, ly, d_in, d_beta, d_out));
+  HIPCHK(hipGetLastError());
+  return RONK_OK;
+}
+
+// the transcript for the layers [l0, l1) (and u when d_final is given), one lane
+static int fri_transcript_dev(const ronk_fri* h, const FriSmall& sm, const u64* d_seed, const u64* d_roots, u32 l0, u32 l1,
+                              const u64* d_final, hipStream_t s) {
+  const ronk_poseidon* pos = h->pos;
+  POS_DISPATCH(pos, hipLaunchKernelGGL((fri_transcript_kernel<FLD, W>), dim3(1), dim3(64), 0, s, pos->sp, (u32)h->sh.d, d_seed, sm.chain,
+                                       d_roots, l0, l1, sm.betas, d_final, h->sh.size(h->sh.layers), sm.u));
+  HIPCHK(hipGetLastError());
+  return RONK_OK;
+}
+static int fri_indices_dev(const ronk_fri* h, const FriSmall& sm, hipStream_t s) {
+  const ronk_poseidon* pos = h->pos;
+  POS_DISPATCH(pos, hipLaunchKernelGGL((fri_index_kernel<FLD, W>), dim3(grid_for(h->sh.queries)), dim3(256), 0, s, pos->sp, (u32)h->sh.d,
+                                       sm.u, h->d_layers, h->sh.layers, h->sh.queries, sm.idx));
+  HIPCHK(hipGetLastError());
+  return RONK_OK;
+}
+
+extern "C" int ronk_fri_prove_dev(const ronk_fri* h, const uint64_t* d_evals, const uint64_t* d_seed, uint64_t* d_work, uint64_t* d_proof,
+                                  void* stream) {
+  if (!h || !d_evals || !d_seed || !d_work || !d_proof) return RONK_ERR_INVALID;
+  const hipStream_t s = (hipStream_t)stream;
+  const FriShape& sh = h->sh;
+  const u32 L = sh.layers;
+  const u64 A = (u64)1 << sh.eta, D = sh.d, Q = sh.queries;
+  const FriSmall sm(sh, d_work);
+  u64* next = d_work + sh.small_words();
+  std::vector<const u64*> vals(L + 1), trees(L);
+  vals[0] = d_evals;
+  // commit phase: commit layer l, draw beta_l from its root, fold
+  for (u32 l = 0; l < L; l++) {
+    const u64 m = (u64)1 << sh.log2m(l);
+    u64* nxt = next;
+    u64* tree = nxt + sh.size(l + 1);
+    next = tree + sh.tree_words(l);
+    RCHK(ronk_merkle_commit_dev(h->pos, vals[l], m, A, 1, m, D, tree, stream));
+    HIPCHK(hipMemcpyAsync(d_proof + l * D, tree + sh.tree_words(l) - D, D * 8, hipMemcpyDeviceToDevice, s));
+    RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, l, l + 1, nullptr, s));
+    RCHK(ronk_fri_fold_dev(h, l, vals[l], sm.betas + l, nxt, stream));
+    vals[l + 1] = nxt;
+    trees[l] = tree;
+  }
+  u64* d_final = d_proof + L * D;
+  HIPCHK(hipMemcpyAsync(d_final, vals[L], sh.size(L) * 8, hipMemcpyDeviceToDevice, s));
+  RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, L, L, d_final, s));
+  // query phase: the indices, then every layer's leaves and paths
+  RCHK(fri_indices_dev(h, sm, s));
+  for (u32 l = 0; l < L; l++) {
+    const u64 m = (u64)1 << sh.log2m(l);
+    RCHK(ronk_merkle_open_dev(trees[l], m, D, sm.idx + l * Q, Q, d_proof + sh.path_off(l), sm.st, stream));
+    if (h->mont)
+      hipLaunchKernelGGL((fri_gather_kernel<FriMont>), dim3(grid_for(Q * A)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l), sh.eta,
+                         sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
+    else
+      hipLaunchKernelGGL((fri_gather_kernel<FriGl>), dim3(grid_for(Q * A)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l), sh.eta,
+                         sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
+    HIPCHK(hipGetLastError());
+  }
+  return RONK_OK;
+}
+
+extern "C" int ronk_fri_verify_dev(const ronk_fri* h, const uint64_t* d_proof, const uint64_t* d_seed, int* d_status, void* stream) {
+  if (!h || !d_proof || !d_seed || !d_status) return RONK_ERR_INVALID;
+  const hipStream_t s = (hipStream_t)stream;
+  const FriShape& sh = h->sh;
+  const u32 L = sh.layers;
+  const u64 A = (u64)1 << sh.eta, D = sh.d, Q = sh.queries;
+  const FriSmall sm(sh, h->d_vs);
+  int* ok = (int*)(h->d_vs + sh.small_words());
+  const u64* d_final = d_proof + L * D;
+  HIPCHK(hipMemsetAsync(d_status, 0, sizeof(int), s));
+  RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, 0, L, d_final, s));
+  RCHK(fri_indices_dev(h, sm, s));
+  for (u32 l = 0; l < L; l++)
+    RCHK(ronk_merkle_verify_dev(h->pos, d_proof + sh.leaf_off(l), Q, A, A, 1, sm.idx + l * Q, d_proof + sh.path_off(l),
+                                (u64)1 << sh.log2m(l), D, d_proof + l * D, ok + l * Q, stream));
+  FRI_DISPATCH(h, hipLaunchKernelGGL((fri_check_kernel<FF, ETA>), dim3(grid_for(Q)), dim3(256), 0, s, h->k, h->d_layers, L, Q, d_proof,
+                                     (u64)(L * D), sm.betas, sm.idx, ok, d_status));
+  HIPCHK(hipGetLastError());
+  const u32 nl = (u32)sh.size(L), first = nl >> h->log2_blowup;
+  if (first < nl) {
+    if (h->mont) hipLaunchKernelGGL((fri_final_kernel<FriMont>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
+    else hipLaunchKernelGGL((fri_final_kernel<FriGl>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
+    HIPCHK(hipGetLastError());
+  }
+  return RONK_OK;
+}
+
+// ------------------------------------------------------------------------------------- host-pointer forms
+extern "C" int ronk_fri_prove(const ronk_fri* h, const uint64_t* evals, const uint64_t* seed, uint64_t* proof) {
+  if (!h || !evals || !seed || !proof) return RONK_ERR_INVALID;
+  RCHK(need_device());
+  const FriShape& sh = h->sh;
+  DevBuf de, ds, dw, dp;
+  RCHK(de.alloc(sh.size(0) * 8)); RCHK(ds.alloc(sh.d * 8)); RCHK(dw.alloc(sh.workspace_words() * 8)); RCHK(dp.alloc(sh.proof_words() * 8));
+  HIPCHK(hipMemcpy(de.p, evals, sh.size(0) * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ds.p, seed, sh.d * 8, hipMemcpyHostToDevice));
+  RCHK(ronk_fri_prove_dev(h, de.u(), ds.u(), dw.u(), dp.u(), nullptr));
+  HIPCHK(hipMemcpy(proof, dp.p, sh.proof_words() * 8, hipMemcpyDeviceToHost));
+  return RONK_OK;
+}
+
+extern "C" int ronk_fri_verify(const ronk_fri* h, const uint64_t* proof, const uint64_t* seed, int* status) {
+  if (!h || !proof || !seed || !status) return RONK_ERR_INVALID;
+  RCHK(need_device());
+  const FriShape& sh = h->sh;
+  DevBuf dp, ds, dst;
+  RCHK(dp.alloc(sh.proof_words() * 8)); RCHK(ds.alloc(sh.d * 8)); RCHK(dst.alloc(8));
+  HIPCHK(hipMemcpy(dp.p, proof, sh.proof_words() * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(ds.p, seed, sh.d * 8, hipMemcpyHostToDevice));
+  RCHK(ronk_fri_verify_dev(h, dp.u(), ds.u(), (int*)dst.p, nullptr));
+  HIPCHK(hipMemcpy(status, dst.p, sizeof(int), hipMemcpyDeviceToHost));
+  return RONK_OK;
+}
