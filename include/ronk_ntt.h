@@ -622,8 +622,9 @@ int ronk_merkle_verify(const ronk_poseidon* h, const uint64_t* leaves, size_t n_
  *                  (log2_blowup <= log2_final <= 8).
  *        proof     canonical words: [L][D] roots, [N_L] final, then per layer l < L: [Q][A] leaf values, [Q][depth_l][D] paths.
  *                  Indices are not stored.
- *      Parameters and soundness are the caller's concern: the challenge is a BASE-field element, and the query count, the
- *      blowup and the Poseidon constants decide what a proof is worth.  Batched or DEEP composition of several columns is out
+ *      Parameters and soundness are the caller's concern: on a handle of ronk_fri_create the challenge is a BASE-field element
+ *      (ronk_fri_create_ext below draws it from the quadratic extension), and the query count, the blowup and the Poseidon
+ *      constants decide what a proof is worth.  Batched or DEEP composition of several columns is out
  *      of scope: one column per call. */
 typedef struct ronk_fri ronk_fri;
 /* The argument checks of ronk_fri_create, host-side integer logic (p, rate: the Poseidon handle's): 2^log2_n does not divide
@@ -655,6 +656,76 @@ int ronk_fri_verify_dev(const ronk_fri* fri, const uint64_t* d_proof, const uint
 /* Host-pointer forms, synchronous. */
 int ronk_fri_prove(const ronk_fri* fri, const uint64_t* evals, const uint64_t* seed, uint64_t* proof);
 int ronk_fri_verify(const ronk_fri* fri, const uint64_t* proof, const uint64_t* seed, int* status);
+
+/* ---- FRI with extension challenges: the same protocol with every challenge, and so every folded layer, in the quadratic
+ *      extension F_p[t] / (t^2 - w) (see "quadratic extension" below; pairs (c0, c1), PLANAR arrays [2][n]).  A handle made by
+ *      ronk_fri_create_ext is used through ronk_fri_fold_dev / prove_dev / verify_dev / prove / verify / destroy above; the handle
+ *      knows its kind.  The semantics are those of the base form with these changes (restated in tests/fri_ext_ref.py):
+ *        layers    layer 0 is [N_0] base words, embedded as (x, 0), when input_ext = 0, and [2][N_0] planar when input_ext = 1 (a
+ *                  codeword that is already a random combination of columns); every layer l >= 1 and the final layer are
+ *                  planar [2][N_l].
+ *        fold      the same formula with beta in the extension and x_i in the base field; in coefficients still
+ *                  g_k = sum_(j < A) beta^j c_(A k + j).  For ronk_fri_fold_dev, d_beta points at two words and d_out receives
+ *                  [2][N_l / A] canonical words.
+ *        leaves    leaf i of a planar layer is its A c0 values followed by its A c1 values: word j = c A + t of the leaf sits at
+ *                  offset i + j m of the layer (m = N_l / A), so the leaf is leaf_len = 2 A, item_stride = 1, elem_stride = m in
+ *                  the addressing of ronk_merkle_commit_dev.  A base layer 0 keeps leaf_len = A.
+ *        transcript  c_0 = seed;  t_l = sponge(c_l || root_l) squeezing D words, beta_l = (t_l[0], t_l[1]), c_(l+1) = t_l;
+ *                  u = sponge(c_L || final c0 plane || final c1 plane);  query indices as in the base form.
+ *        queries   the fold of the opened leaf of layer l must equal the pair of words at slots s and A + s of the leaf opened at
+ *                  layer l + 1, s = j_l div (N_(l+1) / A), and (final[j], final[N_L + j]) after the last committed layer.  Words
+ *                  are compared as they stand: a word >= p is a mismatch.
+ *        final     both planes are of low degree (the domain is in the base field, so the interpolant's coefficients are
+ *                  low-degree componentwise).
+ *        proof     [L][D] roots, [2][N_L] final, then per layer l < L: [Q][leaf_len_l] leaf values, [Q][depth_l][D] paths; in
+ *                  words  L D + 2 N_L + sum_l Q (leaf_len_l + depth_l D),  leaf_len_0 = A (input_ext = 0) or 2 A, else 2 A.
+ *        workspace planar layers 1 .. L, the trees of layers 0 .. L - 1 (leaf counts, and so tree sizes, are those of the base
+ *                  form) and 2 L + (L + 2) D + L Q + Q words of transcript and query state; in words
+ *                  sum_l (2 N_(l+1) + (2 N_l / A - 1) D) + 2 L + (L + 2) D + L Q + Q.
+ *        status    bits 1 / 2 / 4 as in the base form.
+ *      ronk_fri_check_ext: the codes of ronk_fri_check, then those of ronk_ext2_check(p, w), then RONK_ERR_INVALID for
+ *      digest_len < 2 (a challenge takes two sponge words) and for input_ext other than 0 or 1.  The size functions return 0 for
+ *      shapes that are refused.  One kernel per layer, no host round trip, caller-owned workspace and proof, as in the base form. */
+int ronk_fri_check_ext(uint64_t p, uint32_t rate, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift, uint32_t log2_arity,
+                       uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len, uint32_t input_ext);
+size_t ronk_fri_proof_words_ext(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len,
+                                uint32_t input_ext);
+size_t ronk_fri_workspace_words_ext(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len,
+                                    uint32_t input_ext);
+int ronk_fri_create_ext(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift,
+                        uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len,
+                        uint32_t input_ext);
+
+/* ---- the quadratic extension F_p[t] / (t^2 - w) of a 64-bit prime field: the reference's GaloisField<2, P>
+ *      (src/algebra/field/extension/, arithmetic.rs, gf_101_2.rs; PlutoBaseFieldExtension is p = 101, w = 99 = -2).  An element
+ *      is the pair (c0, c1) = c0 + c1 t, the reference's coeffs in increasing degree.  Arrays are PLANAR: n elements are [2][n]
+ *      words, the c0 plane first and the c1 plane at offset n (the layout of the extension FRI layers; the many-array transform
+ *      over the two planes is the NTT of an extension-valued polynomial).  Inputs may be any 64-bit words and are reduced; outputs
+ *      are canonical.  Goldilocks runs on its own arithmetic, every other odd prime on the Montgomery policy.  `out` may alias an
+ *      input elementwise.  No library workspace is used: every _dev call is legal under stream capture.
+ *      ronk_ext2_check (host-side integer logic): p == 2: RONK_ERR_UNSUPPORTED; a composite p: RONK_ERR_NOT_PRIME; w = 0 (mod p)
+ *      or w a quadratic residue (Euler's criterion): RONK_ERR_INVALID.  Every entry point below checks the same first. */
+int ronk_ext2_check(uint64_t p, uint64_t w);
+int ronk_ext2_vec_add_dev(uint64_t p, uint64_t w, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n, void* stream);
+int ronk_ext2_vec_sub_dev(uint64_t p, uint64_t w, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n, void* stream);
+/* (a0 b0 + w a1 b1, (a0 + a1)(b0 + b1) - a0 b0 - a1 b1) */
+int ronk_ext2_vec_mul_dev(uint64_t p, uint64_t w, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n, void* stream);
+int ronk_ext2_vec_neg_dev(uint64_t p, uint64_t w, const uint64_t* d_a, uint64_t* d_out, size_t n, void* stream);
+/* Mul<PrimeField<P>>: d_s holds n base words, both components of element i are multiplied by d_s[i] */
+int ronk_ext2_vec_mul_base_dev(uint64_t p, uint64_t w, const uint64_t* d_a, const uint64_t* d_s, uint64_t* d_out, size_t n, void* stream);
+/* pow by a u64 exponent (square-and-multiply; pow(_, 0) = (1, 0)) */
+int ronk_ext2_vec_pow_dev(uint64_t p, uint64_t w, const uint64_t* d_a, uint64_t e, uint64_t* d_out, size_t n, void* stream);
+/* inverse(): (a0, -a1) / (a0^2 - w a1^2).  *d_status (may be NULL) is set non-zero when an element is ZERO, and (0, 0) is
+ * written for it -- as ronk_vec_inv_dev reports and writes a zero word. */
+int ronk_ext2_vec_inv_dev(uint64_t p, uint64_t w, const uint64_t* d_a, uint64_t* d_out, size_t n, int* d_status, void* stream);
+/* Host-pointer forms, synchronous.  ronk_ext2_vec_inv: a ZERO element is RONK_ERR_ZERO_INVERSE, as ronk_vec_inv. */
+int ronk_ext2_vec_add(uint64_t p, uint64_t w, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+int ronk_ext2_vec_sub(uint64_t p, uint64_t w, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+int ronk_ext2_vec_mul(uint64_t p, uint64_t w, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n);
+int ronk_ext2_vec_neg(uint64_t p, uint64_t w, const uint64_t* a, uint64_t* out, size_t n);
+int ronk_ext2_vec_mul_base(uint64_t p, uint64_t w, const uint64_t* a, const uint64_t* s, uint64_t* out, size_t n);
+int ronk_ext2_vec_pow(uint64_t p, uint64_t w, const uint64_t* a, uint64_t e, uint64_t* out, size_t n);
+int ronk_ext2_vec_inv(uint64_t p, uint64_t w, const uint64_t* a, uint64_t* out, size_t n);
 
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);

@@ -186,6 +186,25 @@ _SIG = {
     "ronk_fri_verify_dev": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "ronk_fri_prove": (_int, [_vp, _vp, _vp, _vp]),
     "ronk_fri_verify": (_int, [_vp, _vp, _vp, C.POINTER(_int)]),
+    "ronk_fri_check_ext": (_int, [_u64, C.c_uint32, _u64, _u64, C.c_uint32, _u64] + [C.c_uint32] * 6),
+    "ronk_fri_proof_words_ext": (_sz, [C.c_uint32] * 6),
+    "ronk_fri_workspace_words_ext": (_sz, [C.c_uint32] * 6),
+    "ronk_fri_create_ext": (_int, [C.POINTER(_vp), _vp, _u64, _u64, C.c_uint32, _u64] + [C.c_uint32] * 6),
+    "ronk_ext2_check": (_int, [_u64, _u64]),
+    "ronk_ext2_vec_add_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "ronk_ext2_vec_sub_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "ronk_ext2_vec_mul_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "ronk_ext2_vec_neg_dev": (_int, [_u64, _u64, _vp, _vp, _sz, _vp]),
+    "ronk_ext2_vec_mul_base_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
+    "ronk_ext2_vec_pow_dev": (_int, [_u64, _u64, _vp, _u64, _vp, _sz, _vp]),
+    "ronk_ext2_vec_inv_dev": (_int, [_u64, _u64, _vp, _vp, _sz, _vp, _vp]),
+    "ronk_ext2_vec_add": (_int, [_u64, _u64, _vp, _vp, _vp, _sz]),
+    "ronk_ext2_vec_sub": (_int, [_u64, _u64, _vp, _vp, _vp, _sz]),
+    "ronk_ext2_vec_mul": (_int, [_u64, _u64, _vp, _vp, _vp, _sz]),
+    "ronk_ext2_vec_neg": (_int, [_u64, _u64, _vp, _vp, _sz]),
+    "ronk_ext2_vec_mul_base": (_int, [_u64, _u64, _vp, _vp, _vp, _sz]),
+    "ronk_ext2_vec_pow": (_int, [_u64, _u64, _vp, _u64, _vp, _sz]),
+    "ronk_ext2_vec_inv": (_int, [_u64, _u64, _vp, _vp, _sz]),
     "ronk_dev_alloc": (_int, [C.POINTER(_vp), _sz]),
     "ronk_dev_free": (_int, [_vp]),
     "ronk_memcpy_h2d": (_int, [_vp, _vp, _sz]),
@@ -376,17 +395,29 @@ def merkle_open_dev(d_tree, n_leaves, digest_len, d_indices, n_idx, d_paths, d_s
 
 class FriHandle:
     """ronk_fri: one FRI instance (log2_n, coset shift, arity, final size, blowup, queries, digest length) on a PoseidonHandle,
-    which it borrows.  The _dev methods take raw device pointers (int) and enqueue on `stream`."""
+    which it borrows.  The _dev methods take raw device pointers (int) and enqueue on `stream`.  With w (a quadratic non-residue)
+    the challenges and the folded layers live in F_p[t] / (t^2 - w) (ronk_fri_create_ext): layers are planar [2][N], a challenge
+    is two words, and input_ext says whether layer 0 is planar pairs too."""
 
-    def __init__(self, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len):
+    def __init__(self, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, w=None, input_ext=False):
         self.h = _vp()
         self.pos = pos      # keeps the Poseidon handle alive
-        check(lib.ronk_fri_create(C.byref(self.h), pos.h, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries,
-                                  digest_len))
+        self.ext, self.input_ext = w is not None, bool(input_ext)
         self.shape = (log2_n, log2_arity, log2_final, n_queries, digest_len)
+        if w is None:
+            if input_ext:
+                raise RonkPanic(ERR_INVALID, "input_ext needs the extension's w")
+            check(lib.ronk_fri_create(C.byref(self.h), pos.h, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries,
+                                      digest_len))
+            self.proof_words = lib.ronk_fri_proof_words(*self.shape)
+            self.workspace_words = lib.ronk_fri_workspace_words(*self.shape)
+        else:
+            check(lib.ronk_fri_create_ext(C.byref(self.h), pos.h, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup,
+                                          n_queries, digest_len, int(self.input_ext)))
+            self.proof_words = lib.ronk_fri_proof_words_ext(*self.shape, int(self.input_ext))
+            self.workspace_words = lib.ronk_fri_workspace_words_ext(*self.shape, int(self.input_ext))
         self.n, self.arity, self.digest_len = 1 << log2_n, 1 << log2_arity, digest_len
-        self.proof_words = lib.ronk_fri_proof_words(*self.shape)
-        self.workspace_words = lib.ronk_fri_workspace_words(*self.shape)
+        self.input_words = self.n * (2 if self.input_ext else 1)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -407,8 +438,8 @@ class FriHandle:
 
     def prove(self, evals, seed):
         evals, seed = arr(evals), arr(seed)
-        if evals.size != self.n or seed.size != self.digest_len:
-            raise RonkPanic(ERR_INVALID, "evals holds 2^log2_n words, seed digest_len")
+        if evals.size != self.input_words or seed.size != self.digest_len:
+            raise RonkPanic(ERR_INVALID, "evals holds 2^log2_n words ([2][2^log2_n] with input_ext), seed digest_len")
         proof = np.empty(self.proof_words, dtype=np.uint64)
         check(lib.ronk_fri_prove(self.h, ptr(evals), ptr(seed), ptr(proof)))
         return proof

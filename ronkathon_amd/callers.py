@@ -338,15 +338,18 @@ class MerkleTree:
 
 class Fri:
     """The FRI prover and verifier of include/ronk_ntt.h ("FRI") for one column over a 64-bit field: `evals` are the values of a
-    polynomial on the coset coset_shift * <omega_N>, N = 2^log2_n, natural order.  sponge_params as for MerkleTree.  Parameters
-    and soundness (a base-field challenge, the query count, the Poseidon constants) are the caller's concern."""
+    polynomial on the coset coset_shift * <omega_N>, N = 2^log2_n, natural order.  sponge_params as for MerkleTree.  With w, a
+    quadratic non-residue of the field, the challenges and the folded layers live in F_p[t] / (t^2 - w) ("FRI with extension
+    challenges"): a challenge is a pair, folded layers are planar [2][N] words, and with input_ext so is `evals`.  Parameters and
+    soundness (the challenge field, the query count, the Poseidon constants) are the caller's concern."""
 
-    def __init__(self, sponge_params, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, g=None):
+    def __init__(self, sponge_params, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, g=None, w=None,
+                 input_ext=False):
         field = sponge_params[0]
         self.field = field
         self.poseidon = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
         self.handle = L.FriHandle(self.poseidon, field._G if g is None else g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup,
-                                  n_queries, digest_len)
+                                  n_queries, digest_len, w=w, input_ext=input_ext)
         self.log2_n, self.log2_arity = log2_n, log2_arity
 
     def prove(self, evals, seed):
@@ -358,21 +361,26 @@ class Fri:
         return self.handle.verify(proof, seed)
 
     def fold(self, values, beta, layer=0):
-        """one layer of arity 2^log2_arity: N_layer words -> N_layer / arity canonical words"""
+        """one layer of arity 2^log2_arity: N_layer words -> N_layer / arity canonical words.  On an extension handle beta is a
+        pair, the result is planar [2][N_layer / arity], and so are the values of every layer but a base layer 0"""
+        h = self.handle
         v = L.arr(values)
-        n_in = 1 << (self.log2_n - self.log2_arity * layer)
+        n_layer = 1 << (self.log2_n - self.log2_arity * layer)
+        n_in = n_layer * (2 if h.ext and (layer > 0 or h.input_ext) else 1)
         if v.size != n_in:
             raise L.RonkPanic(L.ERR_INVALID, "layer %d holds %d words" % (layer, n_in))
-        n_out = n_in >> self.log2_arity
-        b = L.arr([int(beta)])
+        n_out = (n_layer >> self.log2_arity) * (2 if h.ext else 1)
+        b = L.arr([int(c) for c in beta] if h.ext else [int(beta)])
+        if b.size != (2 if h.ext else 1):
+            raise L.RonkPanic(L.ERR_INVALID, "an extension challenge is a pair")
         out = np.empty(n_out, dtype=np.uint64)
         bufs = [C.c_void_p() for _ in range(3)]
         try:
-            for buf, words in zip(bufs, (n_in, 1, n_out)):
+            for buf, words in zip(bufs, (n_in, b.size, n_out)):
                 L.check(L.lib.ronk_dev_alloc(C.byref(buf), words * 8))
             L.check(L.lib.ronk_memcpy_h2d(bufs[0], L.ptr(v), n_in * 8))
-            L.check(L.lib.ronk_memcpy_h2d(bufs[1], L.ptr(b), 8))
-            self.handle.fold_dev(layer, bufs[0], bufs[1], bufs[2])
+            L.check(L.lib.ronk_memcpy_h2d(bufs[1], L.ptr(b), b.size * 8))
+            h.fold_dev(layer, bufs[0], bufs[1], bufs[2])
             L.check(L.lib.ronk_dev_sync())
             L.check(L.lib.ronk_memcpy_d2h(L.ptr(out), bufs[2], n_out * 8))
         finally:

@@ -20,6 +20,7 @@
 //
 // Plain C++ on uint32 / uint64, so tests/emu/emu_fri.cpp compiles the same bodies for the host.
 #pragma once
+#include "ext2.h"
 #include "field_policy.h"
 #include "poseidon_kernels.h"
 
@@ -53,11 +54,23 @@ struct FriGl {
   RONK_HD u64 in(u64 x) const { return gl64::canon(x); }
   RONK_HD u64 out(u64 x) const { return x; }
   RONK_HD u64 add(u64 a, u64 b) const { return gl64::add(a, b); }
+  RONK_HD u64 sub(u64 a, u64 b) const { return gl64::sub(a, b); }
+  RONK_HD u64 neg(u64 a) const { return gl64::neg(a); }
   RONK_HD u64 mul(u64 a, u64 b) const { return gl64::mul(a, b); }
+  RONK_HD u64 mul_w(u64 a, u64 w) const { return gl64::mul(a, w); }   // the extension's product with W (ext2.h)
+  RONK_HD u64 one() const { return 1; }
+  RONK_HD u64 order() const { return gl64::P; }
   template <int N, int J>
   RONK_HD u64 sub_root(u64 a, u64 b) const { return f.template sub_mul_root<N, J, true>(a, b); }   // (a - b) w_N^-J
   template <int ETA>
   RONK_HD u64 fin(u64 x) const { return gl64::mul_2exp_neg<96 - ETA>(x); }   // 2^-eta = 2^(192 - eta) = -2^(96 - eta)
+};
+
+// FriGl for the extension with W = 7: the product with W is 8 x - x, a shift and a subtraction (fewer
+// VALU instructions in the fold's listing than the ordinary product)
+struct FriGlW7 : FriGl {
+  RONK_HD explicit FriGlW7(const FriConsts& k) : FriGl(k) {}
+  RONK_HD u64 mul_w(u64 a, u64) const { return gl64::sub(gl64::mul_2exp<3>(a), a); }
 };
 
 struct FriMont {
@@ -67,7 +80,12 @@ struct FriMont {
   RONK_HD u64 in(u64 x) const { return mont64::mmul(f.f, x, f.f.r2); }   // any 64-bit x -> x R mod p
   RONK_HD u64 out(u64 x) const { return mont64::from_mont(f.f, x); }
   RONK_HD u64 add(u64 a, u64 b) const { return f.add(a, b); }
+  RONK_HD u64 sub(u64 a, u64 b) const { return f.sub(a, b); }
+  RONK_HD u64 neg(u64 a) const { return mont64::neg(f.f, a); }
   RONK_HD u64 mul(u64 a, u64 b) const { return f.mul(a, b); }
+  RONK_HD u64 mul_w(u64 a, u64 w) const { return f.mul(a, w); }
+  RONK_HD u64 one() const { return f.f.one; }
+  RONK_HD u64 order() const { return f.f.p; }
   template <int N, int J>
   RONK_HD u64 sub_root(u64 a, u64 b) const { return f.template sub_mul_root<N, J, true>(a, b); }
   template <int ETA>
@@ -75,19 +93,74 @@ struct FriMont {
 };
 
 // ---------------------------------------------------------------------------------------------------- fold
+// What a layer's values are.  FriWord: base words, multiplier a base word (the base form).  FriPair: pairs of the quadratic
+// extension (ext2.h), multiplier a pair; the in-leaf roots and 2^-eta stay base-field values and act on each component.
+template <class F>
+struct FriWord {
+  typedef u64 V;
+  const F& f;
+  RONK_HD explicit FriWord(const F& base) : f(base) {}
+  RONK_HD u64 add(u64 a, u64 b) const { return f.add(a, b); }
+  RONK_HD u64 mul(u64 a, u64 g) const { return f.mul(a, g); }
+  RONK_HD u64 sqr(u64 g) const { return f.mul(g, g); }
+  template <int N, int J>
+  RONK_HD u64 sub_root(u64 a, u64 b) const { return f.template sub_root<N, J>(a, b); }
+  template <int ETA>
+  RONK_HD u64 fin(u64 a) const { return f.template fin<ETA>(a); }
+};
+template <class F>
+struct FriPair {
+  typedef E2 V;
+  const Ext2<F>& x;
+  RONK_HD explicit FriPair(const Ext2<F>& ext) : x(ext) {}
+  RONK_HD E2 add(E2 a, E2 b) const { return x.add(a, b); }
+  RONK_HD E2 mul(E2 a, E2 g) const { return x.mul(a, g); }
+  RONK_HD E2 sqr(E2 g) const { return x.sqr(g); }
+  template <int N, int J>
+  RONK_HD E2 sub_root(E2 a, E2 b) const {
+    return E2{x.f.template sub_root<N, J>(a.c0, b.c0), x.f.template sub_root<N, J>(a.c1, b.c1)};
+  }
+  template <int ETA>
+  RONK_HD E2 fin(E2 a) const { return E2{x.f.template fin<ETA>(a.c0), x.f.template fin<ETA>(a.c1)}; }
+};
+
 // the butterflies (T - 1, T - 1 + H), ..., (0, H) of one step with multiplier gm
-template <class F, int H, int T>
+template <class O, int H, int T>
 struct FriStep {
-  static RONK_HD void run(const F& f, u64* v, u64 gm) {
-    FriStep<F, H, T - 1>::run(f, v, gm);
-    const u64 a = v[T - 1], b = v[T - 1 + H];
-    v[T - 1] = f.add(f.add(a, b), f.mul(f.template sub_root<2 * H, T - 1>(a, b), gm));
+  typedef typename O::V V;
+  static RONK_HD void run(const O& o, V* v, V gm) {
+    FriStep<O, H, T - 1>::run(o, v, gm);
+    const V a = v[T - 1], b = v[T - 1 + H];
+    v[T - 1] = o.add(o.add(a, b), o.mul(o.template sub_root<2 * H, T - 1>(a, b), gm));
+  }
+};
+template <class O, int H>
+struct FriStep<O, H, 0> {
+  static RONK_HD void run(const O&, typename O::V*, typename O::V) {}
+};
+// the first step of an extension fold over BASE values: (a + b) + gamma ((a - b) w^-t) with a base difference is a product of
+// a pair by a base element, two base products instead of three and no product with W
+template <class F, int H, int T>
+struct FriMixStep {
+  static RONK_HD void run(const F& f, const u64* b, E2* v, E2 gm) {
+    FriMixStep<F, H, T - 1>::run(f, b, v, gm);
+    const u64 d = f.template sub_root<2 * H, T - 1>(b[T - 1], b[T - 1 + H]);
+    v[T - 1] = E2{f.add(f.add(b[T - 1], b[T - 1 + H]), f.mul(d, gm.c0)), f.mul(d, gm.c1)};
   }
 };
 template <class F, int H>
-struct FriStep<F, H, 0> {
-  static RONK_HD void run(const F&, u64*, u64) {}
+struct FriMixStep<F, H, 0> {
+  static RONK_HD void run(const F&, const u64*, E2*, E2) {}
 };
+
+// the steps from butterfly distance H0 = 2^(ETA0 - 1) down to 1 on values already in register form; v[0] is the result before
+// the product with 2^-eta
+template <class O, int ETA0>
+RONK_HD void fri_fold_steps(const O& o, typename O::V* v, typename O::V gm) {
+  if constexpr (ETA0 >= 3) { FriStep<O, 4, 4>::run(o, v, gm); gm = o.sqr(gm); }
+  if constexpr (ETA0 >= 2) { FriStep<O, 2, 2>::run(o, v, gm); gm = o.sqr(gm); }
+  if constexpr (ETA0 >= 1) FriStep<O, 1, 1>::run(o, v, gm);
+}
 
 // one output of a layer from its coset: load(t) = word t of the leaf (any 64-bit value), gamma = beta / x_i in register form;
 // returns the canonical word
@@ -97,11 +170,31 @@ RONK_HD u64 fri_fold_leaf(const F& f, u64 gamma, Load&& load) {
   u64 v[A];
 #pragma unroll
   for (int t = 0; t < A; t++) v[t] = f.in(load(t));
-  u64 gm = gamma;
-  if constexpr (ETA >= 3) { FriStep<F, 4, 4>::run(f, v, gm); gm = f.mul(gm, gm); }
-  if constexpr (ETA >= 2) { FriStep<F, 2, 2>::run(f, v, gm); gm = f.mul(gm, gm); }
-  FriStep<F, 1, 1>::run(f, v, gm);
-  return f.template fin<ETA>(v[0]);
+  const FriWord<F> o(f);
+  fri_fold_steps<FriWord<F>, ETA>(o, v, gamma);
+  return o.template fin<ETA>(v[0]);
+}
+
+// the same with the challenge, and so every folded value, in the quadratic extension: gamma = beta / x_i is a pair in register
+// form.  EXT_IN: the leaf is 2 A words, load(c * A + t) = component c of value t (a planar layer); else A base words embedded
+// as (x, 0), and the first step is the mixed one.  Returns the canonical pair.
+template <class F, int ETA, bool EXT_IN, class Load>
+RONK_HD E2 fri_fold_leaf_ext(const Ext2<F>& x, E2 gamma, Load&& load) {
+  constexpr int A = 1 << ETA;
+  const FriPair<F> o(x);
+  E2 v[A];
+  if constexpr (EXT_IN) {
+#pragma unroll
+    for (int t = 0; t < A; t++) v[t] = E2{x.f.in(load(t)), x.f.in(load(A + t))};
+    fri_fold_steps<FriPair<F>, ETA>(o, v, gamma);
+  } else {
+    u64 b[A];
+#pragma unroll
+    for (int t = 0; t < A; t++) b[t] = x.f.in(load(t));
+    FriMixStep<F, A / 2, A / 2>::run(x.f, b, v, gamma);
+    fri_fold_steps<FriPair<F>, ETA - 1>(o, v, x.sqr(gamma));
+  }
+  return o.template fin<ETA>(v[0]);
 }
 
 // beta / x_i for leaf i < 2^log2m of a layer, beta in register form
@@ -110,6 +203,12 @@ RONK_HD u64 fri_gamma(const F& f, const FriLayer& ly, u64 i, u64 beta) {
   const FriTable hi = (FriTable)ly.hi, lo = (FriTable)ly.lo;
   const u64 xinv = f.mul(hi[i >> ly.kbits], lo[i & (((u64)1 << ly.kbits) - 1)]);
   return f.mul(xinv, beta);
+}
+// the same for a challenge in the extension: 1 / x_i is a base element
+template <class F>
+RONK_HD E2 fri_gamma_ext(const Ext2<F>& x, const FriLayer& ly, u64 i, E2 beta) {
+  const FriTable hi = (FriTable)ly.hi, lo = (FriTable)ly.lo;
+  return x.mul_base(beta, x.f.mul(hi[i >> ly.kbits], lo[i & (((u64)1 << ly.kbits) - 1)]));
 }
 
 // ---------------------------------------------------------------------------------------------------- transcript
@@ -132,14 +231,15 @@ RONK_HD u64 fri_query_word(const PF& pf, const PoseidonConsts& k, u32 d, const u
 }
 // The whole chain for the layers [l0, l1): chain[0 .. d) = seed (l0 == 0), chain[(l + 1) d ..] = sponge(chain[l d ..] ||
 // roots[l d ..]), betas[l] = its first word; with `fin` (after the last layer, l1 == n_layers) also u.  One lane.
+// Extension challenges (bw == 2): betas[2 l], betas[2 l + 1] = its first two words, and `fin` is both planes, nl = 2 N_L words.
 template <class PF, int W>
 RONK_HD void fri_transcript(const PF& pf, const PoseidonConsts& k, u32 d, const u64* seed, u64* chain, const u64* roots, u32 l0, u32 l1,
-                            u64* betas, const u64* fin, u64 nl, u64* u) {
+                            u64* betas, const u64* fin, u64 nl, u64* u, u32 bw = 1) {
   if (l0 == 0)
     for (u32 j = 0; j < d; j++) chain[j] = seed[j];
   for (u32 l = l0; l < l1; l++) {
     fri_chain_step<PF, W>(pf, k, d, chain + (u64)l * d, roots + (u64)l * d, chain + (u64)(l + 1) * d);
-    betas[l] = chain[(u64)(l + 1) * d];
+    for (u32 b = 0; b < bw; b++) betas[(u64)l * bw + b] = chain[(u64)(l + 1) * d + b];
   }
   if (fin) fri_chain_final<PF, W>(pf, k, d, chain + (u64)l1 * d, fin, nl, u);
 }
@@ -177,6 +277,39 @@ RONK_HD int fri_check_query(const F& f, const FriLayer* layers, u32 n_layers, u6
   return ok;
 }
 
+// The same with extension challenges (include/ronk_ntt.h, "FRI with extension challenges"): a planar leaf is 2 A words, c0 values
+// then c1 values; layer 0 is A base words unless in_ext.  The fold must equal the words at slots s and A + s of the next leaf,
+// s = j_l div m_(l+1), and (final[j], final[N_L + j]) at the end.
+template <class F, int ETA>
+RONK_HD int fri_check_query_ext(const Ext2<F>& x, const FriLayer* layers, u32 n_layers, u64 n_queries, const u64* proof, u64 final_off,
+                                u64 nl, bool in_ext, const u64* betas, const u64* idx, u64 q) {
+  constexpr int A = 1 << ETA;
+  int ok = 1;
+  for (u32 l = 0; l < n_layers; l++) {
+    const FriLayer ly = layers[l];
+    const u64 j = idx[(u64)l * n_queries + q];
+    const E2 gamma = fri_gamma_ext(x, ly, j, E2{x.f.in(betas[2 * l]), x.f.in(betas[2 * l + 1])});
+    E2 got;
+    if (l == 0 && !in_ext) {
+      const u64* leaf = proof + ly.leaf_off + q * A;
+      got = fri_fold_leaf_ext<F, ETA, false>(x, gamma, [&](int t) { return leaf[t]; });
+    } else {
+      const u64* leaf = proof + ly.leaf_off + q * 2 * A;
+      got = fri_fold_leaf_ext<F, ETA, true>(x, gamma, [&](int t) { return leaf[t]; });
+    }
+    E2 want;
+    if (l + 1 < n_layers) {
+      const FriLayer nx = layers[l + 1];
+      const u64* nleaf = proof + nx.leaf_off + q * 2 * A;
+      want = E2{nleaf[j >> nx.log2m], nleaf[A + (j >> nx.log2m)]};
+    } else {
+      want = E2{proof[final_off + j], proof[final_off + nl + j]};
+    }
+    ok &= (got.c0 == want.c0) & (got.c1 == want.c1);
+  }
+  return ok;
+}
+
 // Coefficient k of the interpolant of the final layer, up to the non-zero factor s^-k / n: sum_i final[i] w^-(i k).
 // wtab[j] = w^-j in register form, n a power of two; the result is zero exactly when the coefficient is.
 template <class F>
@@ -190,22 +323,26 @@ RONK_HD u64 fri_final_coeff(const F& f, const u64* wtab, const u64* fin, u32 n, 
 struct FriShape {
   u32 n, eta, log2_final, layers;   // layers = (n - log2_final) / eta committed layers
   u64 queries, d;
+  u32 ext = 0, in_ext = 0;          // extension challenges (layers 1 .. L planar pairs); layer 0 planar pairs too
   u64 size(u32 l) const { return (u64)1 << (n - eta * l); }          // N_l
+  u64 vw(u32 l) const { return ext && (l > 0 || in_ext) ? 2 : 1; }   // words per value of layer l
+  u64 leaf_len(u32 l) const { return vw(l) << eta; }
   u32 log2m(u32 l) const { return n - eta * (l + 1); }               // leaves of layer l = 2^log2m
   u64 tree_words(u32 l) const { return (((u64)2 << log2m(l)) - 1) * d; }
   u64 leaf_off(u32 l) const {
-    u64 off = layers * d + size(layers);
-    for (u32 t = 0; t < l; t++) off += queries * ((u64)1 << eta) + queries * log2m(t) * d;
+    u64 off = layers * d + vw(layers) * size(layers);
+    for (u32 t = 0; t < l; t++) off += queries * leaf_len(t) + queries * log2m(t) * d;
     return off;
   }
-  u64 path_off(u32 l) const { return leaf_off(l) + queries * ((u64)1 << eta); }
+  u64 path_off(u32 l) const { return leaf_off(l) + queries * leaf_len(l); }
   u64 proof_words() const { return leaf_off(layers); }
-  // the transcript's and the openings' small state: betas [L], chain [(L + 1) d], u [d], leaf indices [L][Q], open status [Q]
-  u64 small_words() const { return layers + (layers + 2) * d + layers * queries + queries; }
+  // the transcript's and the openings' small state: betas [L] ([L][2] in the extension), chain [(L + 1) d], u [d], leaf indices
+  // [L][Q], open status [Q]
+  u64 small_words() const { return (ext ? 2 : 1) * layers + (layers + 2) * d + layers * queries + queries; }
   // folded layers 1 .. L, the trees of layers 0 .. L - 1, the small state
   u64 workspace_words() const {
     u64 w = small_words();
-    for (u32 l = 0; l < layers; l++) w += size(l + 1) + tree_words(l);
+    for (u32 l = 0; l < layers; l++) w += vw(l + 1) * size(l + 1) + tree_words(l);
     return w;
   }
 };

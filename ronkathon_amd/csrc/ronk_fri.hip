@@ -1,5 +1,6 @@
 // ronk_fri.hip -- C ABI of libronk_ntt.so, part 9: the FRI prover and verifier over the 64-bit fields, on the Poseidon sponge
-// and Merkle commitment of ronk_hash.hip (csrc/fri_kernels.h).
+// and Merkle commitment of ronk_hash.hip (csrc/fri_kernels.h), with base-field challenges
+// (ronk_fri_create) or challenges and folded layers in the quadratic extension (ronk_fri_create_ext).
 #include "runtime.h"
 #include "hip_launch.h"
 #include "poseidon_handle.h"
@@ -13,6 +14,8 @@ struct ronk_fri {
   u32 log2_blowup;
   bool mont;                    // Montgomery policy (any prime, and Goldilocks under a root convention without shift roots)
   FriConsts k;
+  u64 w_reg = 0;                // extension handles (sh.ext): W in register form
+  bool w7 = false;              // shift roots and W = 7: the product with W is a shift (FriGlW7)
   std::vector<FriLayer> layers;   // host copy; the table pointers are device pointers
   u64* d_tab = nullptr;         // per layer lo, hi; then the final layer's w^-j
   const u64* d_wfin = nullptr;
@@ -26,7 +29,7 @@ struct FriSmall {
   int* st;
   FriSmall(const FriShape& sh, u64* base) {
     betas = base;
-    chain = betas + sh.layers;
+    chain = betas + (sh.ext ? 2 : 1) * sh.layers;
     u = chain + (sh.layers + 1) * sh.d;
     idx = u + sh.d;
     st = (int*)(idx + sh.layers * sh.queries);
@@ -46,6 +49,14 @@ struct FriSmall {
     else FRI_DISPATCH_E(FriGl, (h)->sh.eta, __VA_ARGS__);           \
   } while (0)
 
+// the same for the extension kernels, where Goldilocks with W = 7 has a policy of its own
+#define FRI_DISPATCH_X(h, ...)                                            \
+  do {                                                                    \
+    if ((h)->mont) FRI_DISPATCH_E(FriMont, (h)->sh.eta, __VA_ARGS__);     \
+    else if ((h)->w7) FRI_DISPATCH_E(FriGlW7, (h)->sh.eta, __VA_ARGS__);  \
+    else FRI_DISPATCH_E(FriGl, (h)->sh.eta, __VA_ARGS__);                 \
+  } while (0)
+
 // ------------------------------------------------------------------------------------- kernels
 // one lane per output: A loads at stride m (coalesced across lanes), one store
 template <class F, int ETA>
@@ -58,12 +69,27 @@ __global__ void __launch_bounds__(256) fri_fold_kernel(FriConsts k, FriLayer ly,
     out[i] = fri_fold_leaf<F, ETA>(f, fri_gamma(f, ly, i, b), [&](int t) { return in[i + (u64)t * m]; });
 }
 
+// the extension fold: in is A base words at stride m (EXT_IN = false) or the two planes of N = A m words each; out is planar [2][m]
+template <class F, int ETA, bool EXT_IN>
+__global__ void __launch_bounds__(256) fri_fold_ext_kernel(FriConsts k, u64 w, FriLayer ly, const u64* __restrict__ in,
+                                                           const u64* __restrict__ beta, u64* __restrict__ out) {
+  const F f(k);
+  const Ext2<F> x(f, w);
+  const u64 m = (u64)1 << ly.log2m;
+  const E2 b{f.in(beta[0]), f.in(beta[1])};
+  for (u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x; i < m; i += (u64)gridDim.x * blockDim.x) {
+    const E2 r = fri_fold_leaf_ext<F, ETA, EXT_IN>(x, fri_gamma_ext(x, ly, i, b), [&](int t) { return in[i + (u64)t * m]; });
+    out[i] = r.c0;
+    out[m + i] = r.c1;
+  }
+}
+
 template <class PF, int W>
 __global__ void __launch_bounds__(64) fri_transcript_kernel(PoseidonConsts k, u32 d, const u64* seed, u64* chain, const u64* roots, u32 l0,
-                                                            u32 l1, u64* betas, const u64* fin, u64 nl, u64* u) {
+                                                            u32 l1, u64* betas, const u64* fin, u64 nl, u64* u, u32 bw) {
   if (blockIdx.x || threadIdx.x) return;
   const PF pf(k);
-  fri_transcript<PF, W>(pf, k, d, seed, chain, roots, l0, l1, betas, fin, nl, u);
+  fri_transcript<PF, W>(pf, k, d, seed, chain, roots, l0, l1, betas, fin, nl, u, bw);
 }
 
 template <class PF, int W>
@@ -101,6 +127,22 @@ __global__ void __launch_bounds__(256) fri_check_kernel(FriConsts k, const FriLa
   }
 }
 
+template <class F, int ETA>
+__global__ void __launch_bounds__(256) fri_check_ext_kernel(FriConsts k, u64 w, const FriLayer* __restrict__ layers, u32 n_layers,
+                                                            u64 n_queries, const u64* __restrict__ proof, u64 final_off, u64 nl,
+                                                            u32 in_ext, const u64* __restrict__ betas, const u64* __restrict__ idx,
+                                                            const int* __restrict__ ok, int* status) {
+  const F f(k);
+  const Ext2<F> x(f, w);
+  for (u64 q = blockIdx.x * (u64)blockDim.x + threadIdx.x; q < n_queries; q += (u64)gridDim.x * blockDim.x) {
+    int bits = 0;
+    for (u32 l = 0; l < n_layers; l++)
+      if (!ok[(u64)l * n_queries + q]) bits |= 1;
+    if (!fri_check_query_ext<F, ETA>(x, layers, n_layers, n_queries, proof, final_off, nl, in_ext != 0, betas, idx, q)) bits |= 2;
+    if (bits) atomicOr(status, bits);
+  }
+}
+
 // one workgroup: lane k holds coefficient k of the final layer's interpolant; those from `first` on must vanish (bit 4)
 template <class F>
 __global__ void __launch_bounds__(256) fri_final_kernel(FriConsts k, const u64* __restrict__ wtab, const u64* __restrict__ fin, u32 n,
@@ -108,6 +150,14 @@ __global__ void __launch_bounds__(256) fri_final_kernel(FriConsts k, const u64* 
   const F f(k);
   const u32 c = threadIdx.x;
   if (c >= first && c < n && fri_final_coeff(f, wtab, fin, n, c) != 0) atomicOr(status, 4);
+}
+// the same for a planar final layer: both planes must be of low degree (the domain is in the base field)
+template <class F>
+__global__ void __launch_bounds__(256) fri_final_ext_kernel(FriConsts k, const u64* __restrict__ wtab, const u64* __restrict__ fin, u32 n,
+                                                            u32 first, int* status) {
+  const F f(k);
+  const u32 c = threadIdx.x;
+  if (c >= first && c < n && (fri_final_coeff(f, wtab, fin, n, c) | fri_final_coeff(f, wtab, fin + n, n, c)) != 0) atomicOr(status, 4);
 }
 
 // ------------------------------------------------------------------------------------- arguments and sizes
@@ -127,12 +177,13 @@ extern "C" int ronk_fri_check(uint64_t p, uint32_t rate, uint64_t g, uint32_t lo
   return RONK_OK;
 }
 
-static bool fri_shape(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len, FriShape* sh) {
+static bool fri_shape(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len, FriShape* sh,
+                      uint32_t ext = 0, uint32_t input_ext = 0) {
   if (log2_arity < 1 || log2_arity > 3 || log2_final > 8 || log2_n > 63 || log2_n < log2_final + log2_arity ||
-      (log2_n - log2_final) % log2_arity || !n_queries || !digest_len)
+      (log2_n - log2_final) % log2_arity || !n_queries || !digest_len || (ext && (digest_len < 2 || input_ext > 1)))
     return false;
   sh->n = log2_n; sh->eta = log2_arity; sh->log2_final = log2_final; sh->layers = (log2_n - log2_final) / log2_arity;
-  sh->queries = n_queries; sh->d = digest_len;
+  sh->queries = n_queries; sh->d = digest_len; sh->ext = ext; sh->in_ext = ext ? input_ext : 0;
   return true;
 }
 extern "C" size_t ronk_fri_proof_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len) {
@@ -145,6 +196,25 @@ extern "C" size_t ronk_fri_workspace_words(uint32_t log2_n, uint32_t log2_arity,
   return fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &sh) ? (size_t)sh.workspace_words() : 0;
 }
 
+extern "C" int ronk_fri_check_ext(uint64_t p, uint32_t rate, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift,
+                                  uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len,
+                                  uint32_t input_ext) {
+  RCHK(ronk_fri_check(p, rate, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len));
+  RCHK(ronk_ext2_check(p, w));
+  if (digest_len < 2 || input_ext > 1) return RONK_ERR_INVALID;   // a challenge takes two sponge words
+  return RONK_OK;
+}
+extern "C" size_t ronk_fri_proof_words_ext(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries,
+                                           uint32_t digest_len, uint32_t input_ext) {
+  FriShape sh;
+  return fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &sh, 1, input_ext) ? (size_t)sh.proof_words() : 0;
+}
+extern "C" size_t ronk_fri_workspace_words_ext(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries,
+                                               uint32_t digest_len, uint32_t input_ext) {
+  FriShape sh;
+  return fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &sh, 1, input_ext) ? (size_t)sh.workspace_words() : 0;
+}
+
 // ------------------------------------------------------------------------------------- handle
 extern "C" int ronk_fri_destroy(ronk_fri* h) {
   if (!h) return RONK_ERR_INVALID;
@@ -155,19 +225,18 @@ extern "C" int ronk_fri_destroy(ronk_fri* h) {
   return RONK_OK;
 }
 
-extern "C" int ronk_fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint32_t log2_n, uint64_t coset_shift,
-                               uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len) {
-  if (!out) return RONK_ERR_INVALID;
-  *out = nullptr;
-  if (!pos) return RONK_ERR_INVALID;
-  RCHK(ronk_fri_check(pos->p, pos->rate, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len));
+// ext: the handle of ronk_fri_create_ext (w, input_ext are read); the arguments have passed their check
+static int fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint32_t log2_n, uint64_t coset_shift, uint32_t log2_arity,
+                      uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len, bool ext, uint64_t w,
+                      uint32_t input_ext) {
   RCHK(need_device());
   ronk_fri* h = new ronk_fri;
   h->pos = pos; h->p = pos->p; h->g = g % h->p; h->shift = coset_shift % h->p; h->log2_blowup = log2_blowup;
-  fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &h->sh);
+  fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &h->sh, ext, input_ext);
   const FriShape& sh = h->sh;
   h->mont = !fri_gl_shift_roots(h->p, h->g, sh.eta);
   h->k = fri_host_consts(h->mont, h->p, h->g, sh.eta);
+  if (ext) { h->w_reg = ext2_reg_form(h->mont, h->p, w); h->w7 = !h->mont && w % h->p == 7; }
   // tables: per layer lo then hi, then the final layer's roots
   std::vector<size_t> off(sh.layers + 1);
   size_t words = 0;
@@ -202,11 +271,41 @@ extern "C" int ronk_fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_
   return RONK_OK;
 }
 
+extern "C" int ronk_fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint32_t log2_n, uint64_t coset_shift,
+                               uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len) {
+  if (!out) return RONK_ERR_INVALID;
+  *out = nullptr;
+  if (!pos) return RONK_ERR_INVALID;
+  RCHK(ronk_fri_check(pos->p, pos->rate, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len));
+  return fri_create(out, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, false, 0, 0);
+}
+extern "C" int ronk_fri_create_ext(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift,
+                                   uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries,
+                                   uint32_t digest_len, uint32_t input_ext) {
+  if (!out) return RONK_ERR_INVALID;
+  *out = nullptr;
+  if (!pos) return RONK_ERR_INVALID;
+  RCHK(ronk_fri_check_ext(pos->p, pos->rate, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len,
+                          input_ext));
+  return fri_create(out, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, true, w, input_ext);
+}
+
 // ------------------------------------------------------------------------------------- device entry points
 extern "C" int ronk_fri_fold_dev(const ronk_fri* h, uint32_t layer, const uint64_t* d_in, const uint64_t* d_beta, uint64_t* d_out,
                                  void* stream) {
   if (!h || !d_in || !d_beta || !d_out || layer >= h->sh.layers) return RONK_ERR_INVALID;
   const FriLayer& ly = h->layers[layer];
+  if (h->sh.ext) {
+    // d_beta: two words; d_in: layer `layer` as the handle lays it out; d_out: planar [2][N_l / A]
+    if (h->sh.vw(layer) == 2)
+      FRI_DISPATCH_X(h, hipLaunchKernelGGL((fri_fold_ext_kernel<FF, ETA, true>), dim3(grid_for((size_t)1 << ly.log2m)), dim3(256), 0,
+                                         (hipStream_t)stream, h->k, h->w_reg, ly, d_in, d_beta, d_out));
+    else
+      FRI_DISPATCH_X(h, hipLaunchKernelGGL((fri_fold_ext_kernel<FF, ETA, false>), dim3(grid_for((size_t)1 << ly.log2m)), dim3(256), 0,
+                                         (hipStream_t)stream, h->k, h->w_reg, ly, d_in, d_beta, d_out));
+    HIPCHK(hipGetLastError());
+    return RONK_OK;
+  }
   FRI_DISPATCH(h, hipLaunchKernelGGL((fri_fold_kernel<FF, ETA>), dim3(grid_for((size_t)1 << ly.log2m)), dim3(256), 0, (hipStream_t)stream,
                                      h->k, ly, d_in, d_beta, d_out));
   HIPCHK(hipGetLastError());
@@ -218,7 +317,8 @@ static int fri_transcript_dev(const ronk_fri* h, const FriSmall& sm, const u64* 
                               const u64* d_final, hipStream_t s) {
   const ronk_poseidon* pos = h->pos;
   POS_DISPATCH(pos, hipLaunchKernelGGL((fri_transcript_kernel<FLD, W>), dim3(1), dim3(64), 0, s, pos->sp, (u32)h->sh.d, d_seed, sm.chain,
-                                       d_roots, l0, l1, sm.betas, d_final, h->sh.size(h->sh.layers), sm.u));
+                                       d_roots, l0, l1, sm.betas, d_final, h->sh.vw(h->sh.layers) * h->sh.size(h->sh.layers), sm.u,
+                                       h->sh.ext ? 2u : 1u));
   HIPCHK(hipGetLastError());
   return RONK_OK;
 }
@@ -236,7 +336,7 @@ extern "C" int ronk_fri_prove_dev(const ronk_fri* h, const uint64_t* d_evals, co
   const hipStream_t s = (hipStream_t)stream;
   const FriShape& sh = h->sh;
   const u32 L = sh.layers;
-  const u64 A = (u64)1 << sh.eta, D = sh.d, Q = sh.queries;
+  const u64 D = sh.d, Q = sh.queries, BW = sh.ext ? 2 : 1;
   const FriSmall sm(sh, d_work);
   u64* next = d_work + sh.small_words();
   std::vector<const u64*> vals(L + 1), trees(L);
@@ -245,29 +345,31 @@ extern "C" int ronk_fri_prove_dev(const ronk_fri* h, const uint64_t* d_evals, co
   for (u32 l = 0; l < L; l++) {
     const u64 m = (u64)1 << sh.log2m(l);
     u64* nxt = next;
-    u64* tree = nxt + sh.size(l + 1);
+    u64* tree = nxt + sh.vw(l + 1) * sh.size(l + 1);
     next = tree + sh.tree_words(l);
-    RCHK(ronk_merkle_commit_dev(h->pos, vals[l], m, A, 1, m, D, tree, stream));
+    // a planar layer's leaf is its A c0 values then its A c1 values: word c A + t sits at offset i + (c A + t) m
+    RCHK(ronk_merkle_commit_dev(h->pos, vals[l], m, sh.leaf_len(l), 1, m, D, tree, stream));
     HIPCHK(hipMemcpyAsync(d_proof + l * D, tree + sh.tree_words(l) - D, D * 8, hipMemcpyDeviceToDevice, s));
     RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, l, l + 1, nullptr, s));
-    RCHK(ronk_fri_fold_dev(h, l, vals[l], sm.betas + l, nxt, stream));
+    RCHK(ronk_fri_fold_dev(h, l, vals[l], sm.betas + BW * l, nxt, stream));
     vals[l + 1] = nxt;
     trees[l] = tree;
   }
   u64* d_final = d_proof + L * D;
-  HIPCHK(hipMemcpyAsync(d_final, vals[L], sh.size(L) * 8, hipMemcpyDeviceToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_final, vals[L], sh.vw(L) * sh.size(L) * 8, hipMemcpyDeviceToDevice, s));
   RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, L, L, d_final, s));
   // query phase: the indices, then every layer's leaves and paths
   RCHK(fri_indices_dev(h, sm, s));
   for (u32 l = 0; l < L; l++) {
     const u64 m = (u64)1 << sh.log2m(l);
     RCHK(ronk_merkle_open_dev(trees[l], m, D, sm.idx + l * Q, Q, d_proof + sh.path_off(l), sm.st, stream));
+    const u32 log2_leaf = sh.eta + (sh.vw(l) == 2);   // the 2 A words of a planar leaf are gathered at the same stride m
     if (h->mont)
-      hipLaunchKernelGGL((fri_gather_kernel<FriMont>), dim3(grid_for(Q * A)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l), sh.eta,
-                         sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
+      hipLaunchKernelGGL((fri_gather_kernel<FriMont>), dim3(grid_for(Q << log2_leaf)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l),
+                         log2_leaf, sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
     else
-      hipLaunchKernelGGL((fri_gather_kernel<FriGl>), dim3(grid_for(Q * A)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l), sh.eta,
-                         sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
+      hipLaunchKernelGGL((fri_gather_kernel<FriGl>), dim3(grid_for(Q << log2_leaf)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l),
+                         log2_leaf, sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
     HIPCHK(hipGetLastError());
   }
   return RONK_OK;
@@ -278,7 +380,7 @@ extern "C" int ronk_fri_verify_dev(const ronk_fri* h, const uint64_t* d_proof, c
   const hipStream_t s = (hipStream_t)stream;
   const FriShape& sh = h->sh;
   const u32 L = sh.layers;
-  const u64 A = (u64)1 << sh.eta, D = sh.d, Q = sh.queries;
+  const u64 D = sh.d, Q = sh.queries;
   const FriSmall sm(sh, h->d_vs);
   int* ok = (int*)(h->d_vs + sh.small_words());
   const u64* d_final = d_proof + L * D;
@@ -286,12 +388,23 @@ extern "C" int ronk_fri_verify_dev(const ronk_fri* h, const uint64_t* d_proof, c
   RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, 0, L, d_final, s));
   RCHK(fri_indices_dev(h, sm, s));
   for (u32 l = 0; l < L; l++)
-    RCHK(ronk_merkle_verify_dev(h->pos, d_proof + sh.leaf_off(l), Q, A, A, 1, sm.idx + l * Q, d_proof + sh.path_off(l),
+    RCHK(ronk_merkle_verify_dev(h->pos, d_proof + sh.leaf_off(l), Q, sh.leaf_len(l), sh.leaf_len(l), 1, sm.idx + l * Q, d_proof + sh.path_off(l),
                                 (u64)1 << sh.log2m(l), D, d_proof + l * D, ok + l * Q, stream));
+  const u32 nl = (u32)sh.size(L), first = nl >> h->log2_blowup;
+  if (sh.ext) {
+    FRI_DISPATCH_X(h, hipLaunchKernelGGL((fri_check_ext_kernel<FF, ETA>), dim3(grid_for(Q)), dim3(256), 0, s, h->k, h->w_reg, h->d_layers, L,
+                                       Q, d_proof, (u64)(L * D), (u64)nl, sh.in_ext, sm.betas, sm.idx, ok, d_status));
+    HIPCHK(hipGetLastError());
+    if (first < nl) {
+      if (h->mont) hipLaunchKernelGGL((fri_final_ext_kernel<FriMont>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
+      else hipLaunchKernelGGL((fri_final_ext_kernel<FriGl>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
+      HIPCHK(hipGetLastError());
+    }
+    return RONK_OK;
+  }
   FRI_DISPATCH(h, hipLaunchKernelGGL((fri_check_kernel<FF, ETA>), dim3(grid_for(Q)), dim3(256), 0, s, h->k, h->d_layers, L, Q, d_proof,
                                      (u64)(L * D), sm.betas, sm.idx, ok, d_status));
   HIPCHK(hipGetLastError());
-  const u32 nl = (u32)sh.size(L), first = nl >> h->log2_blowup;
   if (first < nl) {
     if (h->mont) hipLaunchKernelGGL((fri_final_kernel<FriMont>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
     else hipLaunchKernelGGL((fri_final_kernel<FriGl>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
@@ -306,8 +419,8 @@ extern "C" int ronk_fri_prove(const ronk_fri* h, const uint64_t* evals, const ui
   RCHK(need_device());
   const FriShape& sh = h->sh;
   DevBuf de, ds, dw, dp;
-  RCHK(de.alloc(sh.size(0) * 8)); RCHK(ds.alloc(sh.d * 8)); RCHK(dw.alloc(sh.workspace_words() * 8)); RCHK(dp.alloc(sh.proof_words() * 8));
-  HIPCHK(hipMemcpy(de.p, evals, sh.size(0) * 8, hipMemcpyHostToDevice));
+  RCHK(de.alloc(sh.vw(0) * sh.size(0) * 8)); RCHK(ds.alloc(sh.d * 8)); RCHK(dw.alloc(sh.workspace_words() * 8)); RCHK(dp.alloc(sh.proof_words() * 8));
+  HIPCHK(hipMemcpy(de.p, evals, sh.vw(0) * sh.size(0) * 8, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(ds.p, seed, sh.d * 8, hipMemcpyHostToDevice));
   RCHK(ronk_fri_prove_dev(h, de.u(), ds.u(), dw.u(), dp.u(), nullptr));
   HIPCHK(hipMemcpy(proof, dp.p, sh.proof_words() * 8, hipMemcpyDeviceToHost));

@@ -108,6 +108,72 @@ using PlutoBaseField = PrimeField<101>;                       // prime/mod.rs:26
 using PlutoScalarField = PrimeField<17>;                      // prime/mod.rs:30
 using GoldilocksField = PrimeField<RONK_GOLDILOCKS_P>;        // the new 64-bit FiniteField implementor
 
+// ---- GaloisField<2, P> with the irreducible t^2 - W (field/extension/mod.rs, arithmetic.rs, gf_101_2.rs): coeffs in increasing
+//      degree.  Scalar operators are host values; the array forms run on the GPU on PLANAR arrays ([2][n] words, c0 plane first).
+template <uint64_t P, uint64_t W>
+struct GaloisField2 {
+  using Base = PrimeField<P>;
+  std::array<Base, 2> coeffs{};
+  static constexpr uint64_t BASE_ORDER = P;
+  GaloisField2() = default;
+  static GaloisField2 new_(std::array<Base, 2> c) { check(ronk_ext2_check(P, W)); GaloisField2 f; f.coeffs = c; return f; }
+  GaloisField2(Base x) { coeffs = {x, Base::ZERO()}; }                          // From<PrimeField<P>>
+  static GaloisField2 ZERO() { return GaloisField2(); }
+  static GaloisField2 ONE() { return GaloisField2(Base::ONE()); }
+  friend GaloisField2 operator+(GaloisField2 a, GaloisField2 b) { GaloisField2 f; f.coeffs = {a.coeffs[0] + b.coeffs[0], a.coeffs[1] + b.coeffs[1]}; return f; }
+  friend GaloisField2 operator-(GaloisField2 a, GaloisField2 b) { GaloisField2 f; f.coeffs = {a.coeffs[0] - b.coeffs[0], a.coeffs[1] - b.coeffs[1]}; return f; }
+  GaloisField2 operator-() const { return ZERO() - *this; }
+  friend GaloisField2 operator*(GaloisField2 a, GaloisField2 b) {                // the product reduced modulo t^2 - W
+    const Base w = Base::new_(W);
+    GaloisField2 f;
+    f.coeffs = {a.coeffs[0] * b.coeffs[0] + w * a.coeffs[1] * b.coeffs[1], a.coeffs[0] * b.coeffs[1] + a.coeffs[1] * b.coeffs[0]};
+    return f;
+  }
+  friend GaloisField2 operator*(GaloisField2 a, Base s) { GaloisField2 f; f.coeffs = {a.coeffs[0] * s, a.coeffs[1] * s}; return f; }   // Mul<PrimeField<P>>
+  friend GaloisField2 operator+(GaloisField2 a, Base s) { return a + GaloisField2(s); }
+  friend GaloisField2 operator-(GaloisField2 a, Base s) { return a - GaloisField2(s); }
+  Base norm() const { return coeffs[0] * coeffs[0] - Base::new_(W) * coeffs[1] * coeffs[1]; }
+  std::optional<GaloisField2> inverse() const {                                  // (a0, -a1) / norm; None for zero
+    auto n = norm().inverse();
+    if (!n) return std::nullopt;
+    GaloisField2 f; f.coeffs = {coeffs[0] * *n, (-coeffs[1]) * *n}; return f;
+  }
+  friend GaloisField2 operator/(GaloisField2 a, GaloisField2 b) {
+    auto i = b.inverse(); if (!i) throw Panic(RONK_ERR_ZERO_INVERSE); return a * *i;
+  }
+  GaloisField2 pow(uint64_t e) const {
+    GaloisField2 r = ONE(), b = *this;
+    while (e) { if (e & 1) r = r * b; b = b * b; e >>= 1; }
+    return r;
+  }
+  friend bool operator==(GaloisField2 a, GaloisField2 b) { return a.coeffs == b.coeffs; }
+  friend bool operator!=(GaloisField2 a, GaloisField2 b) { return !(a == b); }
+  // array forms on planar words (ronk_ext2_vec_*)
+  static std::vector<uint64_t> vec_add(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) { return vec2(ronk_ext2_vec_add, a, b); }
+  static std::vector<uint64_t> vec_sub(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) { return vec2(ronk_ext2_vec_sub, a, b); }
+  static std::vector<uint64_t> vec_mul(const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) { return vec2(ronk_ext2_vec_mul, a, b); }
+  static std::vector<uint64_t> vec_neg(const std::vector<uint64_t>& a) {
+    std::vector<uint64_t> out(a.size()); check(ronk_ext2_vec_neg(P, W, a.data(), out.data(), a.size() / 2)); return out;
+  }
+  static std::vector<uint64_t> vec_mul_base(const std::vector<uint64_t>& a, const std::vector<uint64_t>& s) {
+    if (a.size() != 2 * s.size()) throw Panic(RONK_ERR_INVALID);
+    std::vector<uint64_t> out(a.size()); check(ronk_ext2_vec_mul_base(P, W, a.data(), s.data(), out.data(), s.size())); return out;
+  }
+  static std::vector<uint64_t> vec_pow(const std::vector<uint64_t>& a, uint64_t e) {
+    std::vector<uint64_t> out(a.size()); check(ronk_ext2_vec_pow(P, W, a.data(), e, out.data(), a.size() / 2)); return out;
+  }
+  static std::vector<uint64_t> vec_inv(const std::vector<uint64_t>& a) {
+    std::vector<uint64_t> out(a.size()); check(ronk_ext2_vec_inv(P, W, a.data(), out.data(), a.size() / 2)); return out;
+  }
+ private:
+  template <class Fn>
+  static std::vector<uint64_t> vec2(Fn fn, const std::vector<uint64_t>& a, const std::vector<uint64_t>& b) {
+    if (a.size() != b.size() || a.size() % 2) throw Panic(RONK_ERR_INVALID);
+    std::vector<uint64_t> out(a.size()); check(fn(P, W, a.data(), b.data(), out.data(), a.size() / 2)); return out;
+  }
+};
+using PlutoBaseFieldExtension = GaloisField2<101, 99>;        // X^2 + 2 over F_101 (gf_101_2.rs)
+
 // ---- bases (polynomial/mod.rs:48-72)
 struct Monomial { friend bool operator==(Monomial, Monomial) { return true; } };
 template <class F> struct Lagrange {

@@ -5,7 +5,10 @@ N_0 elements and the sum of ronk_merkle_commit_dev calls on the same layer shape
 the two derived figures: layer-0 fold / vec_mul, and prove minus the commits' sum.  The Poseidon parameters are TEST parameters
 (width 12, alpha 7, 8 full + 22 partial rounds, rate 8), digest 4, arity 8, 64 queries.
 
-usage: python tools/fri_time.py [--iters 10] [--warmup 2] [--rounds 3] [--log2-sizes 20,22,24] [--field gl]"""
+With --ext the same cases are timed again on a handle with extension challenges (ronk_fri_create_ext, W = the generator; --input-ext:
+layer 0 is planar pairs too) after the base-field ones, in the same run, and a last line per size holds the ratios.
+
+usage: python tools/fri_time.py [--iters 10] [--warmup 2] [--rounds 3] [--log2-sizes 20,22,24] [--field gl] [--ext] [--input-ext]"""
 import argparse
 import json
 import os
@@ -21,6 +24,8 @@ ap.add_argument("--log2-sizes", default="20,22,24")
 ap.add_argument("--field", default="gl")
 ap.add_argument("--eta", type=int, default=3)
 ap.add_argument("--queries", type=int, default=64)
+ap.add_argument("--ext", action="store_true")
+ap.add_argument("--input-ext", action="store_true")
 args = ap.parse_args()
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,6 +104,33 @@ def main():
         print(json.dumps(dict(base, op="derived", verify_status=int(st.item()), fold0_over_vec_mul=round(t_fold[0] / t_mul, 3),
                               folds_sum_ms=round(sum(t_fold), 4), commits_sum_ms=round(sum(t_commit), 4),
                               prove_minus_commits_ms=round(t_prove - sum(t_commit), 4), verify_ms=round(t_verify, 4))), flush=True)
+        if args.ext:
+            base_t = {"fold": t_fold, "prove": t_prove, "verify": t_verify}
+            ie = bool(args.input_ext)
+            frx = L.FriHandle(pos, g, n, g, eta, log2_final, min(BLOWUP, log2_final), Q, DIGEST, w=g, input_ext=ie)
+            bx = dict(base, ext=1, input_ext=int(ie), w=g)
+            pair = lambda k: (ins[k % copies], ins[(k + 1) % copies])      # two planes: two of the rotating arrays
+            planar = [torch.cat(pair(k)) for k in range(min(copies, 8))]
+            beta2 = torch.from_numpy(np.array([123456789, 987654321], dtype=np.uint64).view(np.int64)).cuda()
+            out2 = torch.empty(2 * N, dtype=torch.int64, device="cuda")
+            x_fold = []
+            for l in range(layers):
+                nl = N >> (eta * l)
+                src_l = planar if (l > 0 or ie) else ins
+                x_fold.append(report(dict(bx, op="fold_dev", layer=l, words_in=nl * (2 if (l > 0 or ie) else 1)),
+                                     time_ms(lambda k: frx.fold_dev(l, src_l[k % len(src_l)].data_ptr(), beta2.data_ptr(), out2.data_ptr()))))
+            workx = torch.empty(frx.workspace_words, dtype=torch.int64, device="cuda")
+            proofx = torch.empty(frx.proof_words, dtype=torch.int64, device="cuda")
+            ev = planar if ie else ins
+            x_prove = report(dict(bx, op="prove_dev", proof_words=frx.proof_words, workspace_words=frx.workspace_words),
+                             time_ms(lambda k: frx.prove_dev(ev[k % len(ev)].data_ptr(), seed.data_ptr(), workx.data_ptr(), proofx.data_ptr())))
+            x_verify = report(dict(bx, op="verify_dev"), time_ms(lambda k: frx.verify_dev(proofx.data_ptr(), seed.data_ptr(), st.data_ptr())))
+            torch.cuda.synchronize()
+            print(json.dumps(dict(bx, op="ext_over_base", verify_status=int(st.item()),
+                                  fold=[round(a / b, 3) for a, b in zip(x_fold, base_t["fold"])],
+                                  prove=round(x_prove / base_t["prove"], 3), verify=round(x_verify / base_t["verify"], 3))), flush=True)
+            frx.close()
+            del planar, out2, workx, proofx
         fri.close()
         del ins, src, out, work, proof
         torch.cuda.empty_cache()
