@@ -624,8 +624,8 @@ int ronk_merkle_verify(const ronk_poseidon* h, const uint64_t* leaves, size_t n_
  *                  Indices are not stored.
  *      Parameters and soundness are the caller's concern: on a handle of ronk_fri_create the challenge is a BASE-field element
  *      (ronk_fri_create_ext below draws it from the quadratic extension), and the query count, the blowup and the Poseidon
- *      constants decide what a proof is worth.  Batched or DEEP composition of several columns is out
- *      of scope: one column per call. */
+ *      constants decide what a proof is worth.  One column per call; several committed columns are opened through the batched
+ *      FRI polynomial commitment below. */
 typedef struct ronk_fri ronk_fri;
 /* The argument checks of ronk_fri_create, host-side integer logic (p, rate: the Poseidon handle's): 2^log2_n does not divide
  * p - 1: RONK_ERR_NO_ROOT; log2_final > 8 or n_queries > 2^16: RONK_ERR_UNSUPPORTED; coset_shift = 0 (mod p), log2_arity outside
@@ -662,8 +662,8 @@ int ronk_fri_verify(const ronk_fri* fri, const uint64_t* proof, const uint64_t* 
  *      ronk_fri_create_ext is used through ronk_fri_fold_dev / prove_dev / verify_dev / prove / verify / destroy above; the handle
  *      knows its kind.  The semantics are those of the base form with these changes (restated in tests/fri_ext_ref.py):
  *        layers    layer 0 is [N_0] base words, embedded as (x, 0), when input_ext = 0, and [2][N_0] planar when input_ext = 1 (a
- *                  codeword that is already a random combination of columns); every layer l >= 1 and the final layer are
- *                  planar [2][N_l].
+ *                  codeword that is already a random combination of columns: what ronk_deep_combine_dev writes); every layer
+ *                  l >= 1 and the final layer are planar [2][N_l].
  *        fold      the same formula with beta in the extension and x_i in the base field; in coefficients still
  *                  g_k = sum_(j < A) beta^j c_(A k + j).  For ronk_fri_fold_dev, d_beta points at two words and d_out receives
  *                  [2][N_l / A] canonical words.
@@ -695,6 +695,84 @@ size_t ronk_fri_workspace_words_ext(uint32_t log2_n, uint32_t log2_arity, uint32
 int ronk_fri_create_ext(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift,
                         uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len,
                         uint32_t input_ext);
+/* The Q values j_0 that a proof's transcript implies (what the verifier derives before it checks anything), for both kinds of
+ * handle: d_indices receives n_queries words.  It works in the handle's verifier state: one ronk_fri_verify_dev or
+ * ronk_fri_query_indices_dev call at a time per handle.  Asynchronous. */
+int ronk_fri_query_indices_dev(const ronk_fri* fri, const uint64_t* d_proof, const uint64_t* d_seed, uint64_t* d_indices, void* stream);
+
+/* ---- batched FRI polynomial commitment with DEEP quotients: "these C committed polynomials take these values at the K points
+ *      z_k" for the [C][N] matrix that ronk_lde_batch_dev leaves behind, on top of the Merkle commitment and the extension FRI
+ *      above.  The reference has neither FRI nor DEEP; the semantics are fixed here and restated on Python integers in
+ *      tests/deep_ref.py.  Field, extension (pairs, PLANAR arrays), domain x_i = s w^i (i < N = 2^log2_n), transcript sponge and
+ *      tree are those of "FRI with extension challenges"; A = 2^log2_arity, m = N / A, D = digest_len.
+ *        matrix    M: [C][N] row-major base words, M[c][i] = f_c(x_i) with deg f_c < d = N >> log2_blowup; words >= p are reduced.
+ *        coef      [C][d] row-major, monomial basis, unscaled: sum_j coef[c][j] x_i^j = M[c][i].
+ *        points    z: K extension elements, planar [2][K], chosen by the caller (drawn from their transcript after committing).
+ *        claims    y: planar [2][K C], element k C + c = f_c(z_k) = sum_j coef[c][j] z_k^j.
+ *        commit    leaf j < m holds the C A words M[c][j + t m] in the order c A + t: word q of the leaf sits at offset j + q m,
+ *                  which is leaf_len = C A, item_stride = 1, elem_stride = m in the addressing of ronk_merkle_commit_dev.  One
+ *                  leaf holds every column's values on the coset of FRI's layer-0 leaf j.  root_M: the tree's last D words.
+ *        transcript  a = sponge(seed || root_M || z c0 plane || z c1 plane || y c0 plane || y c1 plane) squeezing D words;
+ *                  alpha = (a[0], a[1]); the FRI seed is a.
+ *        codeword  G[i] = sum_(k < K) sum_(c < C) alpha^(k C + c) (M[c][i] - y[k][c]) / (x_i - z_k), planar [2][N], canonical.
+ *                  1 / (x_i - z_k) = (x_i - z0, z1) / ((x_i - z0)^2 - w z1^2).  The norm is zero only when z_k is the domain
+ *                  point x_i; that term then contributes ZERO (as ronk_ext2_vec_inv_dev writes zero), and status bit 32 is set.
+ *        opening   FRI with extension challenges on G (input_ext = 1) under the seed a -- exactly ronk_fri_prove_dev -- and
+ *                  the matrix leaves at its query indices j_0.
+ *        proof     canonical words: [2][K C] claims; the FRI proof, ronk_fri_proof_words_ext(.., 1) words; [Q][C A] matrix
+ *                  leaf values; [Q][log2 m][D] paths.
+ *        verifier  from root_M, z, the seed and the proof: recomputes a and alpha; runs ronk_fri_verify_dev under the seed a;
+ *                  derives the indices; checks the matrix paths (ronk_merkle_verify_dev); recomputes G[j_0 + t m] for every
+ *                  query and t < A from the opened matrix leaf, the claims, alpha and z, and compares it with words t and A + t
+ *                  of the FRI proof's layer-0 leaf as they stand.
+ *        status    the verifier: bits 1 / 2 / 4 as FRI reports them, 8 a matrix path fails, 16 a DEEP mismatch, 32 some z_k lies
+ *                  on the domain; ronk_pcs_open_dev and ronk_deep_combine_dev: 0 or 32.  Every check runs whatever the others find.
+ *        workspace D + Q words (a, open status), G [2][N], then ronk_fri_workspace_words_ext(.., 1) words.
+ *      ronk_pcs_check: the codes of ronk_fri_check_ext with input_ext = 1, then RONK_ERR_INVALID for n_columns = 0 or n_points = 0,
+ *      then RONK_ERR_UNSUPPORTED for n_columns > 1024, n_points > 8 or log2_n < 2.  The size functions return 0 for shapes that are
+ *      refused.  Every _dev call is asynchronous on `stream` with no host round trip (alpha and the indices stay in device
+ *      memory) and uses no library workspace; workspace and proof are caller-owned.  The handle keeps the domain's point table,
+ *      the small table of the call in flight and the verifier's state: one call at a time per handle.  Goldilocks runs on its
+ *      own arithmetic (with w = 7 the product with w is a shift), every other odd prime on the Montgomery policy. */
+typedef struct ronk_pcs ronk_pcs;
+int ronk_pcs_check(uint64_t p, uint32_t rate, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift, uint32_t log2_arity,
+                   uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len, uint32_t n_columns,
+                   uint32_t n_points);
+size_t ronk_pcs_proof_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len,
+                            uint32_t n_columns, uint32_t n_points);
+size_t ronk_pcs_workspace_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len,
+                                uint32_t n_columns, uint32_t n_points);
+/* The handle owns an extension FRI handle with input_ext = 1 and borrows `pos`, which must outlive it. */
+int ronk_pcs_create(ronk_pcs** out, const ronk_poseidon* pos, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift,
+                    uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len,
+                    uint32_t n_columns, uint32_t n_points);
+int ronk_pcs_destroy(ronk_pcs* pcs);
+/* y = the values of n_columns base-field polynomials of d >= 1 coefficients each (d_coef: [n_columns][d] row-major) at n_points
+ * <= 8 points of the extension (d_z: planar [2][n_points]); d_y: planar [2][n_points n_columns], element k n_columns + c.  Any
+ * odd prime p with w a non-residue (ronk_ext2_check); n_columns = 0, n_points = 0 or d = 0: RONK_ERR_INVALID.  The coefficient
+ * matrix is read once for all points. */
+int ronk_ext2_poly_eval_batch_dev(uint64_t p, uint64_t w, const uint64_t* d_coef, uint32_t n_columns, size_t d, const uint64_t* d_z,
+                                  uint32_t n_points, uint64_t* d_y, void* stream);
+int ronk_ext2_poly_eval_batch(uint64_t p, uint64_t w, const uint64_t* coef, uint32_t n_columns, size_t d, const uint64_t* z,
+                              uint32_t n_points, uint64_t* y);
+/* The codeword G as a building block: d_alpha points at two words in device memory (as ronk_fri_fold_dev takes beta), d_G
+ * receives [2][N] canonical words, *d_status 0 or 32.  The matrix is read once; G is the only N-sized write. */
+int ronk_deep_combine_dev(const ronk_pcs* pcs, const uint64_t* d_M, const uint64_t* d_y, const uint64_t* d_z, const uint64_t* d_alpha,
+                          uint64_t* d_G, int* d_status, void* stream);
+/* The tree of the matrix into the caller-owned d_tree, ronk_merkle_tree_words(N / A, D) words. */
+int ronk_pcs_commit_dev(const ronk_pcs* pcs, const uint64_t* d_M, uint64_t* d_tree, void* stream);
+/* d_tree: what ronk_pcs_commit_dev wrote for d_M; d_coef: [C][d]; d_z: [2][K]; d_seed: D words; d_work: ronk_pcs_workspace_words
+ * words; d_proof: ronk_pcs_proof_words words. */
+int ronk_pcs_open_dev(const ronk_pcs* pcs, const uint64_t* d_M, const uint64_t* d_tree, const uint64_t* d_coef, const uint64_t* d_z,
+                      const uint64_t* d_seed, uint64_t* d_work, uint64_t* d_proof, int* d_status, void* stream);
+/* d_root: D words.  The verifier never sees the matrix. */
+int ronk_pcs_verify_dev(const ronk_pcs* pcs, const uint64_t* d_root, const uint64_t* d_z, const uint64_t* d_seed, const uint64_t* d_proof,
+                        int* d_status, void* stream);
+/* Host-pointer forms, synchronous. */
+int ronk_pcs_commit(const ronk_pcs* pcs, const uint64_t* M, uint64_t* tree);
+int ronk_pcs_open(const ronk_pcs* pcs, const uint64_t* M, const uint64_t* tree, const uint64_t* coef, const uint64_t* z,
+                  const uint64_t* seed, uint64_t* proof, int* status);
+int ronk_pcs_verify(const ronk_pcs* pcs, const uint64_t* root, const uint64_t* z, const uint64_t* seed, const uint64_t* proof, int* status);
 
 /* ---- the quadratic extension F_p[t] / (t^2 - w) of a 64-bit prime field: the reference's GaloisField<2, P>
  *      (src/algebra/field/extension/, arithmetic.rs, gf_101_2.rs; PlutoBaseFieldExtension is p = 101, w = 99 = -2).  An element

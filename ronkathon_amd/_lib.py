@@ -190,6 +190,21 @@ _SIG = {
     "ronk_fri_proof_words_ext": (_sz, [C.c_uint32] * 6),
     "ronk_fri_workspace_words_ext": (_sz, [C.c_uint32] * 6),
     "ronk_fri_create_ext": (_int, [C.POINTER(_vp), _vp, _u64, _u64, C.c_uint32, _u64] + [C.c_uint32] * 6),
+    "ronk_fri_query_indices_dev": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ronk_pcs_check": (_int, [_u64, C.c_uint32, _u64, _u64, C.c_uint32, _u64] + [C.c_uint32] * 7),
+    "ronk_pcs_proof_words": (_sz, [C.c_uint32] * 7),
+    "ronk_pcs_workspace_words": (_sz, [C.c_uint32] * 7),
+    "ronk_pcs_create": (_int, [C.POINTER(_vp), _vp, _u64, _u64, C.c_uint32, _u64] + [C.c_uint32] * 7),
+    "ronk_pcs_destroy": (_int, [_vp]),
+    "ronk_ext2_poly_eval_batch_dev": (_int, [_u64, _u64, _vp, C.c_uint32, _sz, _vp, C.c_uint32, _vp, _vp]),
+    "ronk_ext2_poly_eval_batch": (_int, [_u64, _u64, _vp, C.c_uint32, _sz, _vp, C.c_uint32, _vp]),
+    "ronk_deep_combine_dev": (_int, [_vp] * 8),
+    "ronk_pcs_commit_dev": (_int, [_vp, _vp, _vp, _vp]),
+    "ronk_pcs_open_dev": (_int, [_vp] * 10),
+    "ronk_pcs_verify_dev": (_int, [_vp] * 7),
+    "ronk_pcs_commit": (_int, [_vp, _vp, _vp]),
+    "ronk_pcs_open": (_int, [_vp] * 7 + [C.POINTER(_int)]),
+    "ronk_pcs_verify": (_int, [_vp] * 5 + [C.POINTER(_int)]),
     "ronk_ext2_check": (_int, [_u64, _u64]),
     "ronk_ext2_vec_add_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "ronk_ext2_vec_sub_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -451,6 +466,86 @@ class FriHandle:
         st = _int(-1)
         check(lib.ronk_fri_verify(self.h, ptr(proof), ptr(seed), C.byref(st)))
         return st.value
+
+
+class PcsHandle:
+    """ronk_pcs: the batched FRI polynomial commitment with DEEP quotients (include/ronk_ntt.h) for a [n_columns][2^log2_n] matrix
+    opened at n_points points of F_p[t] / (t^2 - w), on a PoseidonHandle, which it borrows.  The _dev methods take raw device
+    pointers (int) and enqueue on `stream`; one call at a time per handle."""
+
+    def __init__(self, pos, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, n_columns, n_points):
+        self.h = _vp()
+        self.pos = pos      # keeps the Poseidon handle alive
+        check(lib.ronk_pcs_create(C.byref(self.h), pos.h, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries,
+                                  digest_len, n_columns, n_points))
+        self.shape = (log2_n, log2_arity, log2_final, n_queries, digest_len, n_columns, n_points)
+        self.proof_words = lib.ronk_pcs_proof_words(*self.shape)
+        self.workspace_words = lib.ronk_pcs_workspace_words(*self.shape)
+        self.n, self.arity, self.digest_len = 1 << log2_n, 1 << log2_arity, digest_len
+        self.columns, self.points, self.coeffs = n_columns, n_points, (1 << log2_n) >> log2_blowup
+        self.tree_words = lib.ronk_merkle_tree_words(self.n >> log2_arity, digest_len)
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib.ronk_pcs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def combine_dev(self, d_M, d_y, d_z, d_alpha, d_G, d_status, stream=0):
+        check(lib.ronk_deep_combine_dev(self.h, d_M, d_y, d_z, d_alpha, d_G, d_status, stream))
+
+    def commit_dev(self, d_M, d_tree, stream=0):
+        check(lib.ronk_pcs_commit_dev(self.h, d_M, d_tree, stream))
+
+    def open_dev(self, d_M, d_tree, d_coef, d_z, d_seed, d_work, d_proof, d_status, stream=0):
+        check(lib.ronk_pcs_open_dev(self.h, d_M, d_tree, d_coef, d_z, d_seed, d_work, d_proof, d_status, stream))
+
+    def verify_dev(self, d_root, d_z, d_seed, d_proof, d_status, stream=0):
+        check(lib.ronk_pcs_verify_dev(self.h, d_root, d_z, d_seed, d_proof, d_status, stream))
+
+    def _sized(self, what, a, words):
+        a = arr(a)
+        if a.size != words:
+            raise RonkPanic(ERR_INVALID, "%s holds %d words" % (what, words))
+        return a
+
+    def commit(self, M):
+        """host matrix [n_columns][2^log2_n] -> the tree (the root is its last digest_len words)"""
+        M = self._sized("the matrix", M, self.columns * self.n)
+        tree = np.empty(self.tree_words, dtype=np.uint64)
+        check(lib.ronk_pcs_commit(self.h, ptr(M), ptr(tree)))
+        return tree
+
+    def open(self, M, tree, coef, z, seed):
+        """-> (the proof, status 0 or 32); z: planar [2][n_points]"""
+        M, tree = self._sized("the matrix", M, self.columns * self.n), self._sized("the tree", tree, self.tree_words)
+        coef = self._sized("the coefficients", coef, self.columns * self.coeffs)
+        z, seed = self._sized("the points", z, 2 * self.points), self._sized("the seed", seed, self.digest_len)
+        proof = np.empty(self.proof_words, dtype=np.uint64)
+        st = _int(-1)
+        check(lib.ronk_pcs_open(self.h, ptr(M), ptr(tree), ptr(coef), ptr(z), ptr(seed), ptr(proof), C.byref(st)))
+        return proof, st.value
+
+    def verify(self, root, z, seed, proof):
+        root, z = self._sized("the root", root, self.digest_len), self._sized("the points", z, 2 * self.points)
+        seed, proof = self._sized("the seed", seed, self.digest_len), self._sized("the proof", proof, self.proof_words)
+        st = _int(-1)
+        check(lib.ronk_pcs_verify(self.h, ptr(root), ptr(z), ptr(seed), ptr(proof), C.byref(st)))
+        return st.value
+
+
+def ext2_poly_eval_batch(p, w, coef, z):
+    """coef: [n_columns][d] base words, z: planar [2][n_points] -> planar [2][n_points n_columns] (ronk_ext2_poly_eval_batch)"""
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.uint64))
+    z = arr(z)
+    if coef.ndim != 2 or z.size % 2:
+        raise RonkPanic(ERR_INVALID, "coef is [n_columns][d], z planar [2][n_points]")
+    c, d, k = coef.shape[0], coef.shape[1], z.size // 2
+    y = np.empty(2 * k * c, dtype=np.uint64)
+    check(lib.ronk_ext2_poly_eval_batch(p, w, ptr(coef), c, d, ptr(z), k, ptr(y)))
+    return y
 
 
 class ShardedPlan:

@@ -5,6 +5,7 @@
 * KZG `open` quotient (reference src/kzg/setup.rs:63-78): poly / (x - z).
 * KZG `commit` / `open` (reference src/kzg/setup.rs:45-78): the multi-scalar multiplication over the SRS.
 * `Poseidon`, `PoseidonSponge` (reference src/hashes/poseidon) and `MerkleTree` (reference src/tree/merkle.rs, over the sponge).
+* `Fri` and `FriPcs` (no counterpart in the reference): FRI for one column, and the batched polynomial commitment on top of it.
 """
 import ctypes as C
 
@@ -388,3 +389,37 @@ class Fri:
                 if buf:
                     L.lib.ronk_dev_free(buf)
         return out
+
+
+class FriPcs:
+    """The batched FRI polynomial commitment of include/ronk_ntt.h ("batched FRI polynomial commitment"): `columns` polynomials of
+    degree below 2^log2_n >> log2_blowup, committed through their values on coset_shift * <omega_N>, are opened at `points` points
+    of F_p[t] / (t^2 - w).  sponge_params as for MerkleTree.  Host arrays in and out; parameters and soundness are the caller's
+    concern, and so is drawing the points after the commitment."""
+
+    def __init__(self, sponge_params, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, columns, points,
+                 g=None):
+        field = sponge_params[0]
+        self.field, self.w = field, w
+        self.poseidon = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
+        self.handle = L.PcsHandle(self.poseidon, field._G if g is None else g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup,
+                                  n_queries, digest_len, columns, points)
+
+    def commit(self, matrix):
+        """[columns][N] values -> the tree; root(tree) is the commitment"""
+        return self.handle.commit(matrix)
+
+    def root(self, tree):
+        return tree[-self.handle.digest_len:]
+
+    def evaluate(self, coeffs, z):
+        """the claims f_c(z_k), planar [2][points columns]; z: planar [2][points]"""
+        return L.ext2_poly_eval_batch(self.field.ORDER, self.w, np.asarray(coeffs, dtype=np.uint64).reshape(self.handle.columns, -1), z)
+
+    def open(self, matrix, tree, coeffs, z, seed):
+        """-> (the proof, ronk_pcs_proof_words canonical words, and the status: 0, or 32 when a point lies on the domain)"""
+        return self.handle.open(matrix, tree, coeffs, z, seed)
+
+    def verify(self, root, z, seed, proof):
+        """-> 0, or bits: 1 / 2 / 4 as FRI reports them, 8 a matrix path fails, 16 a DEEP mismatch, 32 a point on the domain"""
+        return self.handle.verify(root, z, seed, proof)

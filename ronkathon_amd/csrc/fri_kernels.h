@@ -339,6 +339,7 @@ struct FriShape {
   // the transcript's and the openings' small state: betas [L] ([L][2] in the extension), chain [(L + 1) d], u [d], leaf indices
   // [L][Q], open status [Q]
   u64 small_words() const { return (ext ? 2 : 1) * layers + (layers + 2) * d + layers * queries + queries; }
+  u64 idx_off() const { return (ext ? 2 : 1) * layers + (layers + 2) * d; }   // the leaf indices inside that state; layer 0 first
   // folded layers 1 .. L, the trees of layers 0 .. L - 1, the small state
   u64 workspace_words() const {
     u64 w = small_words();

@@ -31,7 +31,7 @@ struct FriSmall {
     betas = base;
     chain = betas + (sh.ext ? 2 : 1) * sh.layers;
     u = chain + (sh.layers + 1) * sh.d;
-    idx = u + sh.d;
+    idx = base + sh.idx_off();
     st = (int*)(idx + sh.layers * sh.queries);
   }
 };
@@ -410,6 +410,22 @@ extern "C" int ronk_fri_verify_dev(const ronk_fri* h, const uint64_t* d_proof, c
     else hipLaunchKernelGGL((fri_final_kernel<FriGl>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
     HIPCHK(hipGetLastError());
   }
+  return RONK_OK;
+}
+
+// where the last verify or query-indices call on the handle left j_0 of every query (runtime.h)
+const u64* fri_handle_indices(const ronk_fri* h) { return h->d_vs + h->sh.idx_off(); }
+
+// the transcript of a proof and its query indices, in the verifier's state; d_indices receives j_0 of every query
+extern "C" int ronk_fri_query_indices_dev(const ronk_fri* h, const uint64_t* d_proof, const uint64_t* d_seed, uint64_t* d_indices,
+                                          void* stream) {
+  if (!h || !d_proof || !d_seed || !d_indices) return RONK_ERR_INVALID;
+  const hipStream_t s = (hipStream_t)stream;
+  const FriShape& sh = h->sh;
+  const FriSmall sm(sh, h->d_vs);
+  RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, 0, sh.layers, d_proof + sh.layers * sh.d, s));
+  RCHK(fri_indices_dev(h, sm, s));
+  HIPCHK(hipMemcpyAsync(d_indices, sm.idx, sh.queries * 8, hipMemcpyDeviceToDevice, s));   // layer 0: j_0 mod m_0 = j_0
   return RONK_OK;
 }
 

@@ -47,6 +47,10 @@ struct FieldCtx;
 bool newton_field(const FieldCtx& f, size_t d, u64* g);
 int newton_ladder_dev(const FieldCtx& fld, u64 G, const u64* f, size_t Lp, u64* g, u64* e, u64* h, u64* t1, hipStream_t s);
 
+// ---- FRI (ronk_fri.hip): the device array in which the last ronk_fri_verify_dev or ronk_fri_query_indices_dev call on the handle
+//      left j_0 of every query, in stream order (ronk_pcs.hip reads it instead of replaying the transcript)
+const u64* fri_handle_indices(const ronk_fri* h);
+
 // ---- host integer logic
 typedef unsigned __int128 u128;
 static inline u64 h_mulmod(u64 a, u64 b, u64 p) { return (u64)(((u128)a * b) % p); }
