@@ -7,6 +7,9 @@ import subprocess
 
 import pytest
 
+import emu_cxx
+import prime_classes as PC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "build", "emu_tile")
 
@@ -45,6 +48,22 @@ def run(emu, *args, env=None):
 MONT_PRIMES = [(0xFFFFFFFC00000001, 10), (29 * 2**57 + 1, 3), (3 * 2**30 + 1, 5)]
 
 
+# mont64::add takes s - p when the sum carried out of bit 63 or s - p did not borrow.  The first prime above all but never has
+# a sum in [p, 2^64), the other two never carry; P_MID (about 3/4 * 2^64, tests/prime_classes.py) takes all three outcomes in
+# every tile.
+P_MID = (PC.P_MID, PC.GEN[PC.P_MID])
+
+
+@pytest.fixture(scope="module")
+def emu_device_form(emu):
+    """the same emulator built with the HIP toolchain's clang++: the `__clang__` branches of mont64.h and gl64.h, the device form
+    of the carry chains (g++ compiles the portable form only)"""
+    src = os.path.join(ROOT, "tests", "emu", "emu_tile.cpp")
+    deps = [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("ntt_tile.h", "ntt_small.h", "ntt_mul.h", "plan.h", "gl64.h", "tile_cfg_table.h",
+                                                                   "field_policy.h", "mont64.h", "ntt_tile_wl.h", "tile_select.h")]
+    return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_tile_clang"), [src, os.path.join(ROOT, "build", "orc_emu.o")], deps)
+
+
 def mont_env(p, g):
     return {"RONK_EMU_P": hex(p), "RONK_EMU_G": str(g)}
 
@@ -70,6 +89,17 @@ def test_montgomery_primes_on_the_tile_kernels(emu, p, g):
         assert "feat:column" in out
         out = run(emu, 20, 1, 1, 2, 18, 25, 0, 700001, 0, 0, 1, env=e)
         assert "feat:column" in out and "feat:row" in out
+
+
+@pytest.mark.parametrize("p,g", [MONT_PRIMES[0], P_MID], ids=["MONT_P", "P_MID"])
+@pytest.mark.parametrize("form", ["portable", "device"])
+def test_add_select_on_the_tile_kernels(request, p, g, form):
+    """one single-pass and one two-pass plan (specialised column / row shapes, inverse) with both forms of mont64.h's carry chains"""
+    exe = request.getfixturevalue("emu" if form == "portable" else "emu_device_form")
+    e = mont_env(p, g)
+    run(exe, 12, 3, 0, 4, env=e)
+    out = run(exe, 16, 2, 1, 4, 18, env=e)
+    assert "cfg:column/matrix" in out and "cfg:row" in out
 
 
 def test_montgomery_fused_multiply_middle(emu):

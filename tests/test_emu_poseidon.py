@@ -7,8 +7,12 @@ import subprocess
 
 import pytest
 
+import emu_cxx
+import prime_classes as PC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GL, MONT, F101 = 0xFFFFFFFF00000001, 0xFFFFFFFC00000001, 101
+P_MID = PC.P_MID     # sums take every outcome of the conditional subtractions (tests/prime_classes.py); MONT all but never has p <= s < 2^64
 
 
 def _build(cmd, out):
@@ -36,6 +40,15 @@ def emu():
 @pytest.fixture(scope="module")
 def emu_eager():
     return _exe("emu_poseidon_eager", ["-DRONK_POSEIDON_LAZY=0"])
+
+
+@pytest.fixture(scope="module")
+def emu_device_form(emu):
+    """the same emulator built with the HIP toolchain's clang++: mont64.h's and poseidon_kernels.h's `__clang__` branches, the device form of the carry
+    chains (g++ compiles the portable form only)"""
+    src = os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp")
+    deps = [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("poseidon_kernels.h", "gl64.h", "mont64.h")]
+    return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_poseidon_clang"), [src], deps, opt="-O1")   # 4 s a run at -O0
 
 
 def run(exe, p, width, alpha, num_p, num_f, rate, seed):
@@ -72,3 +85,17 @@ def test_reduce_after_every_product_form(emu_eager, p):
     """the build-time alternative (RONK_POSEIDON_LAZY=0) computes the same function"""
     assert "lazy=0" in run(emu_eager, p, 12, 7, 5, 4, 8, 21)
     assert "lazy=0" in run(emu_eager, p, 3, 5, 2, 3, 1, 22)
+
+
+def test_p_mid_portable_form(emu):
+    """width 16: the lazy accumulator holds its maximum of 16 products"""
+    run(emu, P_MID, 16, 3, 11, 8, 15, 7)
+    run(emu, P_MID, 2, 7, 3, 4, 1, 8)
+
+
+@pytest.mark.parametrize("p", [GL, MONT, P_MID, PC.P_62])
+def test_device_form_of_the_carry_chains(emu_device_form, p):
+    """PosGl::acc_mad's four-limb chain and PosMont::acc_mad's conditional subtraction as the device compiles them"""
+    run(emu_device_form, p, 16, 3, 11, 8, 15, 7)
+    run(emu_device_form, p, 12, 7, 5, 4, 8, 21)
+    run(emu_device_form, p, 2, 7, 3, 4, 1, 8)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import ext2_ref as ER
+import prime_classes as PC
 from ronkathon_amd import _lib as L
 from ronkathon_amd import extension
 from test_gpu_fri import dev, host, words
@@ -18,6 +19,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GL, MONT = 0xFFFFFFFF00000001, 0xFFFFFFFC00000001
 FIELDS = [(GL, 7), (MONT, 10), (101, 99)]
 SIZES = [1, 63, 64, 65, 4097]   # one lane, the wave boundary, several workgroups with a grid-stride tail
+# MONT's sums all but never land in [p, 2^64): the primes of tests/prime_classes.py take every outcome of mont64::add; W the generator
+CLASS_FIELDS = PC.CLASS_PRIMES
 
 
 @pytest.fixture(scope="module")
@@ -54,9 +57,7 @@ def run_dev(torch, fn, p, w, n, *args, out=None):
     return host(torch, d_out)
 
 
-@pytest.mark.parametrize("p,w", FIELDS)
-@pytest.mark.parametrize("n", SIZES)
-def test_ring_operations(torch, golden, p, w, n):
+def check_ring_operations(torch, golden, p, w, n):
     E = ER.Ext2(p, w)
     a, b = planar_words(n, n, p, golden, "a"), planar_words(n + 1000, n, p, golden, "b")
     ea, eb = els(E, a), els(E, b)
@@ -68,6 +69,18 @@ def test_ring_operations(torch, golden, p, w, n):
     s = words(n + 2000, n, p)
     got = run_dev(torch, L.lib.ronk_ext2_vec_mul_base_dev, p, w, n, d_a, dev(torch, s))
     assert got.tolist() == ER.planar([E.mul_base(x, int(t) % p) for x, t in zip(ea, s)])
+
+
+@pytest.mark.parametrize("p,w", FIELDS)
+@pytest.mark.parametrize("n", SIZES)
+def test_ring_operations(torch, golden, p, w, n):
+    check_ring_operations(torch, golden, p, w, n)
+
+
+@pytest.mark.parametrize("p,w", CLASS_FIELDS)
+@pytest.mark.parametrize("n", SIZES)
+def test_ring_operations_prime_classes(torch, golden, p, w, n):
+    check_ring_operations(torch, golden, p, w, n)
 
 
 def test_golden_vectors_on_the_device(torch, golden):
@@ -88,9 +101,7 @@ def test_golden_vectors_on_the_device(torch, golden):
         assert run_dev(torch, L.lib.ronk_ext2_vec_pow_dev, p, w, 1, d_g, order // q).tolist() != [1, 0]
 
 
-@pytest.mark.parametrize("p,w", FIELDS)
-@pytest.mark.parametrize("n", SIZES)
-def test_inverse(torch, p, w, n):
+def check_inverse(torch, p, w, n):
     E = ER.Ext2(p, w)
     a = planar_words(n + 7, n, p)
     a[0] = 1                                                     # no zero element (c0 of element 0; the others by chance never)
@@ -128,15 +139,24 @@ def test_inverse(torch, p, w, n):
     assert int(d_st.item()) != 0 and host(torch, d_bo)[0] == 0
 
 
+@pytest.mark.parametrize("p,w", FIELDS)
+@pytest.mark.parametrize("n", SIZES)
+def test_inverse(torch, p, w, n):
+    check_inverse(torch, p, w, n)
+
+
+@pytest.mark.parametrize("p,w", CLASS_FIELDS)
+@pytest.mark.parametrize("n", [1, 65])
+def test_inverse_prime_classes(torch, p, w, n):
+    check_inverse(torch, p, w, n)
+
+
 class _Field:
     def __init__(self, p):
         self.ORDER = p
 
 
-@pytest.mark.parametrize("p,w", FIELDS)
-@pytest.mark.parametrize("n", SIZES)
-def test_pow(torch, p, w, n):
-    """every (n, e) against the restatement; a^p = (a0, -a1) (Frobenius) as an independent check"""
+def check_pow(torch, p, w, n):
     E = ER.Ext2(p, w)
     a = planar_words(n + 11, n, p)
     ea = els(E, a)
@@ -146,6 +166,19 @@ def test_pow(torch, p, w, n):
         assert got == ER.planar([E.pow(x, e) for x in ea]), (p, n, e)
         if e == p:
             assert got == ER.planar([(x[0], -x[1] % p) for x in ea]), "Frobenius"
+
+
+@pytest.mark.parametrize("p,w", FIELDS)
+@pytest.mark.parametrize("n", SIZES)
+def test_pow(torch, p, w, n):
+    """every (n, e) against the restatement; a^p = (a0, -a1) (Frobenius) as an independent check"""
+    check_pow(torch, p, w, n)
+
+
+@pytest.mark.parametrize("p,w", CLASS_FIELDS)
+@pytest.mark.parametrize("n", [1, 65])
+def test_pow_prime_classes(torch, p, w, n):
+    check_pow(torch, p, w, n)
 
 
 @pytest.mark.parametrize("p,w", FIELDS)

@@ -11,6 +11,7 @@ import pytest
 
 import fri_ref as FR
 import poseidon_ref as PR
+import prime_classes as PC
 from ronkathon_amd import _lib as L
 from ronkathon_amd import callers
 
@@ -19,6 +20,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [PR.GOLDILOCKS, PR.MONT_P]
 GEN = {PR.GOLDILOCKS: 7, PR.MONT_P: 10}
+# MONT_P's sums all but never land in [p, 2^64): the primes of tests/prime_classes.py take every outcome of mont64::add
+CLASS_FIELDS = PC.CLASS_FIELDS
+GEN.update({p: PC.GEN[p] for p in CLASS_FIELDS})
 Q, D = 8, 2
 CASES = [(6, 1, 2), (9, 3, 3), (12, 2, 4), (12, 3, 3)]
 
@@ -95,12 +99,9 @@ def fold_final(n, eta):
 
 
 # ------------------------------------------------------------------------------------------------ (a) the fold, whole vectors
-@pytest.mark.parametrize("p", FIELDS)
-@pytest.mark.parametrize("eta", [1, 2, 3])
-def test_fold_against_restatement(torch, p, eta):
-    """one lane, one workgroup, several workgroups, both levels of the inverse-point table; s = 1 and s = g; edge words"""
+def check_folds(torch, p, eta, sizes):
     rng = random.Random(eta)
-    for n in (eta + 1, 9, 12, 16):
+    for n in sizes:
         for shift in (1, GEN[p]):
             I = Instance(p, n, eta, fold_final(n, eta), 0, shift=shift)
             v = words(100 * n + eta, 1 << n, p)
@@ -111,6 +112,19 @@ def test_fold_against_restatement(torch, p, eta):
                 I.h.fold_dev(0, d_in.data_ptr(), d_beta.data_ptr(), d_out.data_ptr())
                 assert host(torch, d_out).tolist() == FR.fold(I.F, v, beta, 0), (p, eta, n, shift, beta)
             I.close()
+
+
+@pytest.mark.parametrize("p", FIELDS)
+@pytest.mark.parametrize("eta", [1, 2, 3])
+def test_fold_against_restatement(torch, p, eta):
+    """one lane, one workgroup, several workgroups, both levels of the inverse-point table; s = 1 and s = g; edge words"""
+    check_folds(torch, p, eta, (eta + 1, 9, 12, 16))
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+@pytest.mark.parametrize("eta", [1, 2, 3])
+def test_fold_prime_classes(torch, p, eta):
+    check_folds(torch, p, eta, (eta + 1, 9, 12))
 
 
 @pytest.mark.parametrize("p", FIELDS)
@@ -179,9 +193,7 @@ def reference(p, case):
     return _REF[key]
 
 
-@pytest.mark.parametrize("p", FIELDS)
-@pytest.mark.parametrize("case", CASES)
-def test_proof_word_for_word(torch, p, case):
+def check_proof(torch, p, case):
     n, eta, log2_final = case
     f, seed, want = reference(p, case)
     I = Instance(p, n, eta, log2_final, 1)
@@ -191,6 +203,18 @@ def test_proof_word_for_word(torch, p, case):
     # (f) a second identical call over a differently poisoned workspace: bit-identical
     assert np.array_equal(I.prove_dev(torch, f, seed, fill=0x55), got)
     I.close()
+
+
+@pytest.mark.parametrize("p", FIELDS)
+@pytest.mark.parametrize("case", CASES)
+def test_proof_word_for_word(torch, p, case):
+    check_proof(torch, p, case)
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+@pytest.mark.parametrize("case", CASES[:2])
+def test_proof_word_for_word_prime_classes(torch, p, case):
+    check_proof(torch, p, case)
 
 
 @pytest.fixture(scope="module")
@@ -241,9 +265,7 @@ def test_roots_of_a_large_codeword(torch, cref, p):
 
 
 # ------------------------------------------------------------------------------------------------ (d) the verifier
-@pytest.mark.parametrize("p", FIELDS)
-def test_verifier_statuses(torch, p):
-    case = CASES[1]
+def check_verifier_statuses(torch, p, case):
     n, eta, log2_final = case
     f, seed, proof = reference(p, case)
     I = Instance(p, n, eta, log2_final, 1)
@@ -261,10 +283,12 @@ def test_verifier_statuses(torch, p):
         want = FR.verify(F, bad, seed)
         assert want != 0 and I.verify_dev(torch, bad, seed) == want, (p, what)
     assert FR.verify(F, [proof[i] ^ (1 if i == flips["path"] else 0) for i in range(len(proof))], seed) == 1
-    # a word >= p in the place of its residue is no fold value
-    if proof[off_final] + p < 2**64:
+    # a word >= p in the place of its residue is no fold value: at the final-layer position of the first query (the verifier
+    # compares words there; a position no query reaches only enters the degree check, which reduces it)
+    j = FR.transcript(F, seed, *FR.split(F, proof)[:2])[1][0][F.L - 1]
+    if proof[off_final + j] + p < 2**64:
         bad = list(proof)
-        bad[off_final] += p
+        bad[off_final + j] += p
         want = FR.verify(F, bad, seed)
         assert want & 2 and I.verify_dev(torch, bad, seed) == want
     # another seed
@@ -282,6 +306,17 @@ def test_verifier_statuses(torch, p):
     want = FR.verify(F, pr.tolist(), seed)
     assert want != 0 and I.verify_dev(torch, pr, seed) == want
     I.close()
+
+
+@pytest.mark.parametrize("p", FIELDS)
+def test_verifier_statuses(torch, p):
+    check_verifier_statuses(torch, p, CASES[1])
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+@pytest.mark.parametrize("case", CASES[:2])
+def test_verifier_statuses_prime_classes(torch, p, case):
+    check_verifier_statuses(torch, p, case)
 
 
 # ------------------------------------------------------------------------------------------------ (e) host forms

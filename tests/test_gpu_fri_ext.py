@@ -13,7 +13,7 @@ import fri_ref as FR
 import poseidon_ref as PR
 from ronkathon_amd import _lib as L
 from ronkathon_amd import callers
-from test_gpu_fri import CASES, D, FIELDS, GEN, Q, _Field, dev, fold_final, host, params, words
+from test_gpu_fri import CASES, CLASS_FIELDS, D, FIELDS, GEN, Q, _Field, dev, fold_final, host, params, words
 from test_gpu_fri import reference as base_reference
 
 pytestmark = pytest.mark.gpu
@@ -70,14 +70,9 @@ def want_fold(F, v, beta, layer):
 
 
 # ------------------------------------------------------------------------------------------------ (a) the fold, whole vectors
-@pytest.mark.parametrize("p", FIELDS)
-@pytest.mark.parametrize("eta", [1, 2, 3])
-@pytest.mark.parametrize("input_ext", [0, 1])
-def test_fold_against_restatement(torch, p, eta, input_ext):
-    """one lane, one workgroup, several workgroups, both levels of the inverse-point table; s = 1 and s = g; edge words; beta with
-    zero, one, p - 1 and a word >= p among its components"""
+def check_folds(torch, p, eta, input_ext, sizes):
     rng = random.Random(eta + 10 * input_ext)
-    for n in (eta + 1, 9, 12, 16):
+    for n in sizes:
         for shift in (1, GEN[p]):
             I = Instance(p, n, eta, fold_final(n, eta), 0, input_ext, shift=shift)
             v = words(100 * n + eta, (1 + input_ext) << n, p)
@@ -86,6 +81,23 @@ def test_fold_against_restatement(torch, p, eta, input_ext):
             for beta in betas:
                 assert I.fold_dev(torch, 0, v, beta) == want_fold(I.F, v, beta, 0), (p, eta, n, shift, beta)
             I.close()
+
+
+@pytest.mark.parametrize("p", FIELDS)
+@pytest.mark.parametrize("eta", [1, 2, 3])
+@pytest.mark.parametrize("input_ext", [0, 1])
+def test_fold_against_restatement(torch, p, eta, input_ext):
+    """one lane, one workgroup, several workgroups, both levels of the inverse-point table; s = 1 and s = g; edge words; beta with
+    zero, one, p - 1 and a word >= p among its components"""
+    check_folds(torch, p, eta, input_ext, (eta + 1, 9, 12, 16))
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+@pytest.mark.parametrize("eta", [1, 2, 3])
+@pytest.mark.parametrize("input_ext", [0, 1])
+def test_fold_prime_classes(torch, p, eta, input_ext):
+    """the primes of tests/prime_classes.py (every outcome of mont64::add), several workgroups"""
+    check_folds(torch, p, eta, input_ext, (9,))
 
 
 @pytest.mark.parametrize("p", FIELDS)
@@ -153,10 +165,7 @@ def reference(p, case, input_ext):
     return _REF[key]
 
 
-@pytest.mark.parametrize("p", FIELDS)
-@pytest.mark.parametrize("case", CASES)
-@pytest.mark.parametrize("input_ext", [0, 1])
-def test_proof_word_for_word(torch, p, case, input_ext):
+def check_proof(torch, p, case, input_ext):
     n, eta, log2_final = case
     f, seed, want = reference(p, case, input_ext)
     I = Instance(p, n, eta, log2_final, 1, input_ext)
@@ -166,6 +175,19 @@ def test_proof_word_for_word(torch, p, case, input_ext):
     # a second identical call over a differently poisoned workspace: bit-identical
     assert np.array_equal(I.prove_dev(torch, f, seed, fill=0x55), got)
     I.close()
+
+
+@pytest.mark.parametrize("p", FIELDS)
+@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("input_ext", [0, 1])
+def test_proof_word_for_word(torch, p, case, input_ext):
+    check_proof(torch, p, case, input_ext)
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+@pytest.mark.parametrize("input_ext", [0, 1])
+def test_proof_word_for_word_prime_classes(torch, p, input_ext):
+    check_proof(torch, p, CASES[1], input_ext)
 
 
 # ------------------------------------------------------------------------------------------------ (c) the verifier

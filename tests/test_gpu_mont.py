@@ -4,16 +4,24 @@ src/polynomial/mod.rs:273-323, :430-484).  Whole vectors, bit-exact.  Needs a re
 import numpy as np
 import pytest
 
+import prime_classes as PC
 from conftest import splitmix_field
 
 pytestmark = pytest.mark.gpu
 
 GP = 0xFFFFFFFF00000001
-# (p, primitive element): a prime above 2^63 with 2-adicity 34 (sums carry into bit 64), 29 * 2^57 + 1 (below 2^62:
-# no carries at all), 3 * 2^30 + 1 (a 32-bit prime: high limbs mostly zero), Goldilocks itself with a generator other
-# than the reference's 7 (its shift-twiddle kernels do not apply: the roots are no powers of two)
+# (p, primitive element).  mont64::add takes s - p when the sum s = a + b carried out of bit 63 OR s - p did not borrow; what each
+# prime does and does not exercise of that select (the exact shares are in tests/prime_classes.py):
+#   0xFFFFFFFC00000001, 2-adicity 34, just below 2^64: about half of the sums carry, but a sum in [p, 2^64) -- reduced by the
+#     second term alone -- has probability 10^-9: in effect never
+#   29 * 2^57 + 1 (below 2^62) and 3 * 2^30 + 1 (a 32-bit prime: high limbs mostly zero): about half of the sums lie in [p, 2^64),
+#     none carries
+# so none of the three takes both terms in one run.  P_MID below does: 50 % s < p, 28 % in [p, 2^64), 22 % carried.
+# Goldilocks itself runs with a generator other than the reference's 7 (its shift-twiddle kernels do not apply: the roots are no
+# powers of two)
 PRIMES = [(0xFFFFFFFC00000001, 10), (29 * 2**57 + 1, 3), (3 * 2**30 + 1, 5)]
 GL_OTHER = (GP, 7 * 7 * 7)   # 343 = 7^3: an odd power of a non-residue is a non-residue -- omega_{2^k} keeps its exact order
+P_MID = (PC.P_MID, PC.GEN[PC.P_MID])   # 0xC000002400000001, 2-adicity 34: both terms of the select inside the same tile
 
 
 @pytest.fixture(scope="module")
@@ -54,7 +62,7 @@ def corners(x, p):
     return x
 
 
-@pytest.mark.parametrize("p,g", PRIMES + [GL_OTHER])
+@pytest.mark.parametrize("p,g", PRIMES + [GL_OTHER, P_MID])
 def test_mont_tiled_path_selected(L, p, g):
     for k in (4, 12, 16, 22):
         plan = L.Plan(p, g, k)
@@ -68,10 +76,7 @@ def test_mont_tiled_path_selected(L, p, g):
     plan.close()
 
 
-@pytest.mark.parametrize("p,g", PRIMES + [GL_OTHER])
-@pytest.mark.parametrize("k", [4, 5, 6, 7, 8, 9, 10, 11, 12])
-def test_mont_single_pass_sizes(L, orc, p, g, k):
-    """n <= 2^12: one pass, the batch is the column axis (ragged last tile, staged I/O for n = 16 / 32)"""
+def check_single_pass(L, orc, p, g, k):
     n, batch = 1 << k, 37
     x = corners(splitmix_field(0x600 + k, n * batch, p), p)
     plan = L.Plan(p, g, k, batch)
@@ -86,9 +91,19 @@ def test_mont_single_pass_sizes(L, orc, p, g, k):
 
 
 @pytest.mark.parametrize("p,g", PRIMES + [GL_OTHER])
-@pytest.mark.parametrize("k", [13, 14, 15, 16, 17, 18, 19, 20, 21, 22])
-def test_mont_two_pass_whole_vector(L, orc, p, g, k):
-    """2^13 .. 2^22 (latency kernels up to 2^18, tile kernels above), forward and inverse against the oracle, every element"""
+@pytest.mark.parametrize("k", [4, 5, 6, 7, 8, 9, 10, 11, 12])
+def test_mont_single_pass_sizes(L, orc, p, g, k):
+    """n <= 2^12: one pass, the batch is the column axis (ragged last tile, staged I/O for n = 16 / 32)"""
+    check_single_pass(L, orc, p, g, k)
+
+
+@pytest.mark.parametrize("k", [4, 5, 12])
+def test_mont_single_pass_sizes_p_mid(L, orc, k):
+    """staged I/O (16, 32) and the largest single pass over the prime whose sums take every outcome of mont64::add"""
+    check_single_pass(L, orc, *P_MID, k)
+
+
+def check_two_pass(L, orc, p, g, k):
     n = 1 << k
     x = corners(splitmix_field(0x700 + k, n, p), p)
     plan = L.Plan(p, g, k)
@@ -97,6 +112,20 @@ def test_mont_two_pass_whole_vector(L, orc, p, g, k):
     assert np.array_equal(plan.inverse(x), orc.ifft(p, g, x)), k
     assert np.array_equal(plan.inverse(y), x)
     plan.close()
+
+
+@pytest.mark.parametrize("p,g", PRIMES + [GL_OTHER])
+@pytest.mark.parametrize("k", [13, 14, 15, 16, 17, 18, 19, 20, 21, 22])
+def test_mont_two_pass_whole_vector(L, orc, p, g, k):
+    """2^13 .. 2^22 (latency kernels up to 2^18, tile kernels above), forward and inverse against the oracle, every element"""
+    check_two_pass(L, orc, p, g, k)
+
+
+@pytest.mark.parametrize("k", [13, 16, 19, 20, 21, 22])
+def test_mont_two_pass_whole_vector_p_mid(L, orc, k):
+    """the latency kernels (13, 16), the 8-column tiles (19) and the wave-local passes of 2^10 and 2^11 rows (20, 21, 22) over
+    the prime whose sums take every outcome of mont64::add"""
+    check_two_pass(L, orc, *P_MID, k)
 
 
 @pytest.mark.parametrize("p,g", PRIMES[:2])
@@ -208,7 +237,7 @@ def test_mont_dist_phases_one_process_per_rank_protocol(L, orc):
         assert np.array_equal(out, orc.fft(p, g, x)), (log2n, W, chunks)
 
 
-@pytest.mark.parametrize("p,g", PRIMES + [GL_OTHER])
+@pytest.mark.parametrize("p,g", PRIMES + [GL_OTHER, P_MID])
 def test_mont_poly_mul_ntt_path(L, orc, p, g):
     """Polynomial Mul (src/polynomial/arithmetic.rs:97-119) through the Montgomery NTT path: schoolbook oracle at small sizes,
     three oracle transforms at large ones; ragged lengths, the pair plan and its padding limits"""

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+import prime_classes as PC
 import ronkathon_amd as R
 from ronkathon_amd import _lib as L
 from ronkathon_amd.callers import poly_eval_many, poly_interpolate
@@ -132,9 +133,7 @@ def coeff_counts(m):
     return [1, m, 3 * m + 7] + ([2**16] if m == 4096 else [])
 
 
-@pytest.mark.parametrize("m", SIZES)
-@pytest.mark.parametrize("p", PRIMES)
-def test_eval_many_against_oracle_both_forms(torch, p, m):
+def check_eval_many_both_forms(torch, p, m):
     for d in coeff_counts(m):
         c = field_vec(m * 31 + d, d, p)
         x = points_with_repeats(m * 7 + d, m, p)
@@ -149,6 +148,18 @@ def test_eval_many_against_oracle_both_forms(torch, p, m):
         check_values(p, c, x, direct)
         for other in (tree, tree_dev, direct_dev, auto):
             assert np.array_equal(other, direct), (p, m, d)
+
+
+@pytest.mark.parametrize("m", SIZES)
+@pytest.mark.parametrize("p", PRIMES)
+def test_eval_many_against_oracle_both_forms(torch, p, m):
+    check_eval_many_both_forms(torch, p, m)
+
+
+@pytest.mark.parametrize("m", [65, 4096])
+def test_eval_many_both_forms_p_mid(torch, m):
+    """one leaf past the first and a full tree over the prime whose sums take every outcome of mont64::add (tests/prime_classes.py)"""
+    check_eval_many_both_forms(torch, PC.P_MID, m)
 
 
 def test_eval_many_unreduced_points_and_python_mirrors():

@@ -13,7 +13,7 @@ import fri_ref as FR
 import poseidon_ref as PR
 from ronkathon_amd import _lib as L
 from ronkathon_amd import callers
-from test_gpu_fri import CASES, D, FIELDS, GEN, Q, _Field, dev, fold_final, host, params, words
+from test_gpu_fri import CASES, CLASS_FIELDS, D, FIELDS, GEN, Q, _Field, dev, fold_final, host, params, words
 from test_gpu_fri import reference as base_reference
 from test_gpu_fri_ext import reference as ext_reference
 
@@ -77,15 +77,15 @@ class Instance:
 
 
 # ------------------------------------------------------------------------------------------------ (a) evaluation at extension points
-@pytest.mark.parametrize("p", FIELDS)
-def test_eval_batch_against_restatement(torch, p):
-    """one and several rounds per lane with a partial last round (d around the 256 lanes of a workgroup), one and several columns,
-    edge words in the coefficients; points zero, one, t, random and with components >= p"""
+EVAL_CASES = [(1, 1, 1), (1, 33, 3), (2, 3, 3), (255, 16, 1), (256, 33, 3), (257, 3, 3), (257, 1, 1), (4096, 16, 3), (4096, 3, 1)]
+
+
+def check_eval_batch(torch, p, cases):
     E = ER.Ext2(p, GEN[p])
     rng = random.Random(3)
     special = [(0, 0), (1, 0), (0, 1), (rng.randrange(p), rng.randrange(p)), (p + 1, p + 2) if p + 2 < 2**64 else (p, 2**64 - 1)]
-    cases = [(1, 1, 1), (1, 33, 3), (2, 3, 3), (255, 16, 1), (256, 33, 3), (257, 3, 3), (257, 1, 1), (4096, 16, 3), (4096, 3, 1)]
-    for it, (d, C, K) in enumerate(cases):
+    for d, C, K in cases:
+        it = EVAL_CASES.index((d, C, K))
         coef = words(50 + it, C * d, p).reshape(C, d)
         zs = [special[(it + k) % 5] for k in range(K)] if d < 4096 else [special[3], special[4], special[2]][:K]
         want = ER.planar([DR.evaluate_ext(E, coef[c].tolist(), z) for z in zs for c in range(C)])
@@ -95,6 +95,19 @@ def test_eval_batch_against_restatement(torch, p):
         assert host(torch, d_y).tolist() == want, (p, d, C, K)
         if d <= 257:
             assert L.ext2_poly_eval_batch(p, GEN[p], coef, np.array(ER.planar(zs), dtype=np.uint64)).tolist() == want, (p, d, C, K)
+
+
+@pytest.mark.parametrize("p", FIELDS)
+def test_eval_batch_against_restatement(torch, p):
+    """one and several rounds per lane with a partial last round (d around the 256 lanes of a workgroup), one and several columns,
+    edge words in the coefficients; points zero, one, t, random and with components >= p"""
+    check_eval_batch(torch, p, EVAL_CASES)
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+def test_eval_batch_prime_classes(torch, p):
+    """the primes of tests/prime_classes.py (every outcome of mont64::add): a partial last round, and a full one with 33 columns"""
+    check_eval_batch(torch, p, [(257, 3, 3), (256, 33, 3)])
 
 
 # ------------------------------------------------------------------------------------------------ (b) the DEEP codeword
@@ -113,19 +126,10 @@ def combine_case(torch, I, M, d_M, rng, alpha, on_domain=None, base_point=False)
     assert got_st == st and got == ER.planar(want), (p, S.F.n, S.F.eta, S.C, S.K, alpha, on_domain, base_point)
 
 
-@pytest.mark.parametrize("p", FIELDS)
-@pytest.mark.parametrize("eta", [1, 2, 3])
-def test_combine_against_restatement(torch, p, eta):
-    """one lane, one workgroup, several workgroups, both levels of the point table; one and several columns and points; s = 1 and
-    s = g; alpha with zero, one, p - 1 and a word >= p among its components; a base-field point off the domain (status 0) and a
-    domain point (status 32, the term is zero)"""
+def check_combine(torch, p, eta, shapes):
     rng = random.Random(eta)
     rnd = (rng.randrange(p), rng.randrange(p))
     alphas = ((0, 0), (1, 0), (0, 1), (p - 1, p - 1), rnd, (p + 1 if p + 1 < 2**64 else p, rng.randrange(p)))
-    shapes = {eta + 1: [(C, K, s) for C in (1, 2, 16, 33) for K in (1, 2, 3) for s in ((1,) if (C + K) % 2 else (GEN[p],))],
-              9: [(1, 1, 1), (2, 2, GEN[p]), (16, 3, 1), (33, 1, GEN[p])],
-              12: [(16, 2, GEN[p]), (33, 3, 1)],
-              16: [(2, 1, GEN[p])]}
     for n, cases in shapes.items():
         for C, K, shift in cases:
             I = Instance(p, n, eta, fold_final(n, eta), 0, C, K, shift=shift)
@@ -138,6 +142,27 @@ def test_combine_against_restatement(torch, p, eta):
                 combine_case(torch, I, M, d_M, rng, rnd, on_domain=(1 << n) - 1)
                 combine_case(torch, I, M, d_M, rng, rnd, on_domain=0)
             I.close()
+
+
+@pytest.mark.parametrize("p", FIELDS)
+@pytest.mark.parametrize("eta", [1, 2, 3])
+def test_combine_against_restatement(torch, p, eta):
+    """one lane, one workgroup, several workgroups, both levels of the point table; one and several columns and points; s = 1 and
+    s = g; alpha with zero, one, p - 1 and a word >= p among its components; a base-field point off the domain (status 0) and a
+    domain point (status 32, the term is zero)"""
+    check_combine(torch, p, eta, {eta + 1: [(C, K, s) for C in (1, 2, 16, 33) for K in (1, 2, 3) for s in ((1,) if (C + K) % 2 else (GEN[p],))],
+                                  9: [(1, 1, 1), (2, 2, GEN[p]), (16, 3, 1), (33, 1, GEN[p])],
+                                  12: [(16, 2, GEN[p]), (33, 3, 1)],
+                                  16: [(2, 1, GEN[p])]})
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+@pytest.mark.parametrize("eta", [1, 2, 3])
+def test_combine_prime_classes(torch, p, eta):
+    """the primes of tests/prime_classes.py (every outcome of mont64::add): one lane and several workgroups, one and 33 columns,
+    one and three points, s = 1 and s = g; the base-field point and the domain points (status 32) with each"""
+    corners = [(1, 1, 1), (1, 3, GEN[p]), (33, 1, GEN[p]), (33, 3, 1)]
+    check_combine(torch, p, eta, {eta + 1: corners, 9: corners})
 
 
 def test_goldilocks_with_another_w(torch):
@@ -221,9 +246,7 @@ def instance_of(p, oc):
     return Instance(p, n, eta, log2_final, log2_blowup, C, K)
 
 
-@pytest.mark.parametrize("p", FIELDS)
-@pytest.mark.parametrize("oc", OPEN_CASES)
-def test_proof_word_for_word(torch, p, oc):
+def check_proof(torch, p, oc):
     coef, M, zs, tree, want = reference(p, oc)
     I = instance_of(p, oc)
     d_M = dev(torch, np.array(M, dtype=np.uint64).ravel())
@@ -242,6 +265,18 @@ def test_proof_word_for_word(torch, p, oc):
 
 
 @pytest.mark.parametrize("p", FIELDS)
+@pytest.mark.parametrize("oc", OPEN_CASES)
+def test_proof_word_for_word(torch, p, oc):
+    check_proof(torch, p, oc)
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+@pytest.mark.parametrize("oc", [OPEN_CASES[1], OPEN_CASES[2]])
+def test_proof_word_for_word_prime_classes(torch, p, oc):
+    check_proof(torch, p, oc)
+
+
+@pytest.mark.parametrize("p", FIELDS + CLASS_FIELDS)
 @pytest.mark.parametrize("oc", [OPEN_CASES[1], OPEN_CASES[2]])
 def test_verifier_statuses(torch, p, oc):
     coef, M, zs, tree, proof = reference(p, oc)

@@ -12,6 +12,7 @@ import pytest
 
 import oracle as orc
 import poseidon_ref as PR
+import prime_classes as PC
 import ronkathon_amd as R
 from ronkathon_amd import _lib as L
 from ronkathon_amd import callers
@@ -21,6 +22,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GP, GG = R.GOLDILOCKS_P, R.GOLDILOCKS_G
 FIELDS = [PR.GOLDILOCKS, PR.MONT_P]
+# MONT_P's sums all but never land in [p, 2^64) and never in a tile together with a carry: the primes of tests/prime_classes.py
+# take every outcome of mont64::add and of PosMont::acc_mad's conditional subtraction
+CLASS_FIELDS = PC.CLASS_FIELDS
+CLASS_WIDTHS = (2, 8, 12, 16)     # the register widths' ends; at 16 the lazy accumulator holds its maximum of 16 products
 
 
 @pytest.fixture(scope="module")
@@ -98,9 +103,8 @@ def test_reference_vector_f101():
     assert sp.absorb([1, 2, 3]).absorb(list(range(20))).squeeze(9) == PR.sponge(P6, [1, 2, 3] + list(range(20)), 9)
 
 
-@pytest.mark.parametrize("p", FIELDS)
-def test_permutation_all_widths(torch, p):
-    for width in range(2, 17):
+def check_permutation(torch, p, widths):
+    for width in widths:
         alpha = (3, 5, 7, 11)[width % 4]
         P = PR.derive_params(p, width, alpha, 3, 4 + (width & 1), max(1, width - 1))
         h = handle(P)
@@ -116,8 +120,17 @@ def test_permutation_all_widths(torch, p):
 
 
 @pytest.mark.parametrize("p", FIELDS)
-def test_sponge_all_widths_both_layouts(torch, p):
-    for width in range(2, 17):
+def test_permutation_all_widths(torch, p):
+    check_permutation(torch, p, range(2, 17))
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+def test_permutation_prime_classes(torch, p):
+    check_permutation(torch, p, CLASS_WIDTHS)
+
+
+def check_sponge(torch, p, widths):
+    for width in widths:
         for rate in sorted({1, max(1, width // 2), width - 1}):
             alpha = (3, 5, 7, 11)[(width + rate) % 4]
             P = PR.derive_params(p, width, alpha, 3, 4, rate)
@@ -138,6 +151,16 @@ def test_sponge_all_widths_both_layouts(torch, p):
                 if length == 0:
                     assert all(v == 0 for w in want_all for v in w[:rate])     # no permutation before the first rate outputs
             h.close()
+
+
+@pytest.mark.parametrize("p", FIELDS)
+def test_sponge_all_widths_both_layouts(torch, p):
+    check_sponge(torch, p, range(2, 17))
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+def test_sponge_both_layouts_prime_classes(torch, p):
+    check_sponge(torch, p, CLASS_WIDTHS)
 
 
 def _check_tree(torch, P, h, n, leaf_len, d, seed):
@@ -226,6 +249,15 @@ def test_merkle_against_python_tree(torch, p):
     h = handle(P)
     for n, d in ((257, 8), (5, 1), (300, 4)):
         _check_tree(torch, P, h, n, 9, d, 2000 + n)
+    h.close()
+
+
+@pytest.mark.parametrize("p", CLASS_FIELDS)
+def test_merkle_odd_level_prime_classes(torch, p):
+    """300 leaves: more than one workgroup of 256 nodes, and the levels 75 and 19 are odd (the last node pairs with itself)"""
+    P = PR.derive_params(p, 12, 7, 2, 2, 8)
+    h = handle(P)
+    _check_tree(torch, P, h, 300, 9, 4, 2300)
     h.close()
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+import prime_classes as PC
 import ronkathon_amd as R
 from ronkathon_amd import _lib as L
 from ronkathon_amd.callers import Message, poly_from_roots
@@ -191,6 +192,11 @@ def test_recover_goldilocks_all_erasure_sets(torch, log2n):
 @pytest.mark.parametrize("log2n", [16, 20])
 def test_recover_montgomery(torch, p, g, log2n):
     check_sets(torch, p, g, log2n, 2 if log2n == 16 else 1, (1 << log2n) // 2, log2n)
+
+
+def test_recover_montgomery_p_mid(torch):
+    """two rows at 2^16 over the prime whose sums take every outcome of mont64::add (tests/prime_classes.py)"""
+    check_sets(torch, PC.P_MID, PC.GEN[PC.P_MID], 16, 2, 1 << 15, 16)
 
 
 def test_recover_matches_decode_for_small_k(torch):

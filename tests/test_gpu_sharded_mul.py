@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+import prime_classes as PC
 import ronkathon_amd as R
 from ronkathon_amd import _lib as L
 from ronkathon_amd import dist
@@ -88,9 +89,7 @@ def test_fused_and_composed_middles_agree(log2n, W, chunks):
     fused.close(); comp.close()
 
 
-@pytest.mark.parametrize("p,g", MONT)
-@pytest.mark.parametrize("log2n,W,chunks", [(16, 2, 1), (20, 8, 2), (24, 4, 4)])
-def test_sharded_mul_montgomery(p, g, log2n, W, chunks):
+def check_sharded_mul_montgomery(p, g, log2n, W, chunks):
     n = 1 << log2n
     a, b = field_vec(0x5EED7400 + log2n, n // 2, p), field_vec(0x5EED7500 + log2n, n // 2 - 3, p)
     want = cyclic(p, g, a, b, n)[:a.size + b.size - 1]
@@ -99,6 +98,17 @@ def test_sharded_mul_montgomery(p, g, log2n, W, chunks):
         assert mp.fused_middle == (0 if unfused else int(fusable(log2n, W, mp.chunks)))
         assert np.array_equal(mp.mul(a, b), want), (p, log2n, W, chunks, unfused)
         mp.close()
+
+
+@pytest.mark.parametrize("p,g", MONT)
+@pytest.mark.parametrize("log2n,W,chunks", [(16, 2, 1), (20, 8, 2), (24, 4, 4)])
+def test_sharded_mul_montgomery(p, g, log2n, W, chunks):
+    check_sharded_mul_montgomery(p, g, log2n, W, chunks)
+
+
+def test_sharded_mul_montgomery_p_mid():
+    """the fused and the composed middle at 2^20 over the prime whose sums take every outcome of mont64::add (tests/prime_classes.py)"""
+    check_sharded_mul_montgomery(PC.P_MID, PC.GEN[PC.P_MID], 20, 8, 2)
 
 
 class Blocks:
