@@ -39,6 +39,23 @@
 #define RONK_ASM_NOP1 "s_nop 1\n\t"
 #endif
 
+// Branch census (tests/emu only, host compilers only; the device build and every product build see an empty macro): with
+// -DRONK_GL64_CENSUS each function below reports which of its outcomes it took -- carry / ">= p" / neither, borrow or not,
+// a non-canonical operand of a product -- to counters the emulator points `cur` at (tests/test_emu_gl_branches.py).
+#if defined(RONK_GL64_CENSUS) && !defined(__HIP_DEVICE_COMPILE__) && !defined(__HIPCC__)
+namespace gl64 {
+namespace census {
+enum Fn { ADD, ADD_LAZY, MAD_EPS_CANON, SUB, SUB32, MUL, NFN };
+enum { NONE = 0, WRAP = 1, GE_P = 2, NOUT = 3 };   // sub / sub32: NONE = no borrow, WRAP = borrow; mul: GE_P = an operand >= p
+inline unsigned long long (*cur)[NOUT] = nullptr;   // [NFN][NOUT] of the current (pass, phase); null = not counting
+inline void hit(int fn, int outcome) { if (cur) cur[fn][outcome]++; }
+}  // namespace census
+}  // namespace gl64
+#define RONK_GL64_HIT(fn, outcome) ::gl64::census::hit(::gl64::census::fn, (outcome))
+#else
+#define RONK_GL64_HIT(fn, outcome) ((void)0)
+#endif
+
 namespace gl64 {
 
 typedef uint64_t u64;
@@ -54,6 +71,7 @@ RONK_HD u64 canon(u64 x) { return x + ((x >= P) ? EPS : 0); }
 // prime/arithmetic.rs:3-7.  a, b < p: a wrapped sum (s < a) or s >= p both mean "subtract p"
 RONK_HD u64 add(u64 a, u64 b) {
   u64 s = a + b;
+  RONK_GL64_HIT(ADD, s < a ? census::WRAP : s >= P ? census::GE_P : census::NONE);
 #ifdef RONK_GL64_ALL_LAZY   // tools/census.hip only: instruction-count upper bound for deferred canonicalisation (WRONG values)
   return s + ((s < a) ? EPS : 0);
 #else
@@ -84,6 +102,7 @@ RONK_HD u64 mad_eps_canon(u32 h, u64 t) {
   return r;
 #else
   u64 r = (u64)h * 0xFFFFFFFFu + t;
+  RONK_GL64_HIT(MAD_EPS_CANON, r < t ? census::WRAP : r >= P ? census::GE_P : census::NONE);
   return r + ((r < t || r >= P) ? EPS : 0);
 #endif
 }
@@ -94,6 +113,7 @@ RONK_HD u64 sub(u64 a, u64 b);
 // only the wrap is folded back (2^64 = EPS), the ">= p" test of add() is skipped.  Result in [0, 2^64), == a + b (mod p).
 RONK_HD u64 add_lazy(u64 a, u64 b) {
   u64 s = a + b;
+  RONK_GL64_HIT(ADD_LAZY, s < a ? census::WRAP : s >= P ? census::GE_P : census::NONE);   // GE_P: the result is not canonical
   return s + ((s < a) ? EPS : 0);   // after a wrap s <= p - 2, so + EPS cannot wrap again
 }
 
@@ -115,6 +135,7 @@ RONK_HD u64 sub32(u64 a, u32 h) {
       : "vcc", "scc");
   return ((u64)hi << 32) | lo;
 #else
+  RONK_GL64_HIT(SUB32, a < (u64)h ? census::WRAP : census::NONE);
   return sub(a, (u64)h);
 #endif
 }
@@ -122,6 +143,7 @@ RONK_HD u64 sub32(u64 a, u32 h) {
 // a - b, + p on borrow (prime/arithmetic.rs:19-28).  Also valid for ANY a < 2^64 and b <= p; the
 // result is then some representative in [0, 2^64).
 RONK_HD u64 sub(u64 a, u64 b) {
+  RONK_GL64_HIT(SUB, a < b ? census::WRAP : census::NONE);
 #if defined(__clang__) && !(RONK_GL64_VARIANT & 1)
   u32 b1, b2, b3, b4;
   u32 lo = __builtin_subc((u32)a, (u32)b, 0u, &b1);
@@ -158,6 +180,7 @@ RONK_HD u64 reduce128(u64 lo, u64 hi) {
 
 // prime/arithmetic.rs:34-38.  Schoolbook on 32-bit limbs; each line is one v_mad_u64_u32.
 RONK_HD u64 mul(u64 a, u64 b) {
+  RONK_GL64_HIT(MUL, (a >= P || b >= P) ? census::GE_P : census::NONE);
   u32 a0 = (u32)a, a1 = (u32)(a >> 32), b0 = (u32)b, b1 = (u32)(b >> 32);
   u64 p00 = (u64)a0 * b0;
   u64 p01 = (u64)a0 * b1 + (p00 >> 32);

@@ -8,6 +8,10 @@
 //
 // usage: emu_tile <log2n> <batch> <inverse 0|1> <max_logc> [twf_max_log] [three_pass_from] [in_valid] [out_valid] [auto_tiles] [in_valid1]
 //        (prints OK or the first mismatch)
+// RONK_EMU_INPUT / RONK_EMU_INPUT2: files of raw little-endian u64 words that replace the generated input (n * batch words; the
+// second operand in the in2 and `mul` modes: there the files hold d and d2 words; `dist`: n words).  Built with
+// -DRONK_GL64_CENSUS the emulator also prints how often every gl64.h function took each of its outcomes, per (pass, phase):
+// the phase of a work-item is the number of barriers it has passed (wave-local bodies: barriers / wave_syncs, counted apart).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,7 +39,60 @@ struct FiberArgs {
 };
 static FiberArgs g_fa;
 
-static void fiber_barrier() { swapcontext(&g_ctx[g_cur], &g_sched); }
+// ---- branch census (gl64.h, -DRONK_GL64_CENSUS): counters keyed by (pass, barriers passed, wave_syncs passed)
+#ifdef RONK_GL64_CENSUS
+static constexpr int CEN_PASSES = 16, CEN_PH = 24;
+static unsigned long long g_census[CEN_PASSES][CEN_PH][CEN_PH][gl64::census::NFN][gl64::census::NOUT];
+static std::vector<int> g_nbar, g_nsync;   // per fiber
+static int g_census_pass = 0;
+static void census_enter(int tid) {
+  if (g_census_pass >= CEN_PASSES || g_nbar[tid] >= CEN_PH || g_nsync[tid] >= CEN_PH) { fprintf(stderr, "census table too small\n"); abort(); }
+  gl64::census::cur = g_census[g_census_pass][g_nbar[tid]][g_nsync[tid]];
+}
+static void census_leave() { gl64::census::cur = nullptr; }
+static void census_reset(size_t T) { g_nbar.assign(T, 0); g_nsync.assign(T, 0); }
+static void census_set_pass(int p) { g_census_pass = p; }
+static void census_print() {
+  static const char* const fn[] = {"add", "add_lazy", "mad_eps_canon", "sub", "sub32", "mul"};
+  static const char* const oc[gl64::census::NFN][gl64::census::NOUT] = {
+      {"none", "wrap", "ge_p"}, {"none", "wrap", "ge_p"}, {"none", "wrap", "ge_p"}, {"none", "borrow", "-"}, {"none", "borrow", "-"},
+      {"canonical", "-", "operand_ge_p"}};
+  for (int p = 0; p < CEN_PASSES; p++)
+    for (int b = 0; b < CEN_PH; b++)
+      for (int w = 0; w < CEN_PH; w++)
+        for (int f = 0; f < gl64::census::NFN; f++) {
+          unsigned long long tot = 0;
+          for (int o = 0; o < gl64::census::NOUT; o++) tot += g_census[p][b][w][f][o];
+          if (!tot) continue;
+          for (int o = 0; o < gl64::census::NOUT; o++)
+            if (oc[f][o][0] != '-') printf("census pass=%d phase=%d.%d fn=%s outcome=%s count=%llu\n", p, b, w, fn[f], oc[f][o], g_census[p][b][w][f][o]);
+        }
+}
+#define CENSUS_BAR(t) g_nbar[t]++
+#define CENSUS_SYNC(t) g_nsync[t]++
+#else
+static void census_enter(int) {}
+static void census_leave() {}
+static void census_reset(size_t) {}
+static void census_set_pass(int) {}
+static void census_print() {}
+#define CENSUS_BAR(t) ((void)0)
+#define CENSUS_SYNC(t) ((void)0)
+#endif
+
+static void fiber_barrier() { CENSUS_BAR(g_cur); swapcontext(&g_ctx[g_cur], &g_sched); }
+// the wave-local bodies' second callback (ntt_tile_wl.h wave_sync): the same yield, its own census counter
+static void fiber_wave_sync() { CENSUS_SYNC(g_cur); swapcontext(&g_ctx[g_cur], &g_sched); }
+
+// RONK_EMU_INPUT / RONK_EMU_INPUT2: `count` raw little-endian u64 words from the named file; false = variable not set
+static bool load_words(const char* env, uint64_t* dst, size_t count) {
+  const char* path = getenv(env);
+  if (!path || !*path) return false;
+  FILE* fp = fopen(path, "rb");
+  if (!fp || fread(dst, 8, count, fp) != count || fgetc(fp) != EOF) { fprintf(stderr, "%s: cannot read exactly %zu words from %s\n", env, count, path); exit(2); }
+  fclose(fp);
+  return true;
+}
 
 // RONK_EMU_P / RONK_EMU_G: run the Montgomery instantiations (field_policy.h MontField) for this odd prime and primitive
 // element instead of the Goldilocks ones -- the same plan builder, tables in Montgomery form, the oracle called with (p, g)
@@ -56,9 +113,9 @@ static bool run_choice(int logr, u32 tid) {
       u32* l32 = reinterpret_cast<u32*>(g_fa.lds);
 #define EMU_WL_RUN(LR, FULLIMG)                                                                                                  \
   do {                                                                                                                           \
-    if (c.kind == 1) tile_body_wl_col<LR, INV, 1, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);            \
-    else if (c.kind == 3) tile_body_wl_col<LR, INV, 3, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);       \
-    else tile_body_wl_row<LR, INV, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_barrier);                           \
+    if (c.kind == 1) tile_body_wl_col<LR, INV, 1, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_wave_sync);          \
+    else if (c.kind == 3) tile_body_wl_col<LR, INV, 3, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_wave_sync);     \
+    else tile_body_wl_row<LR, INV, FULLIMG, FLD>(a, l32, tid, g_fa.bid, fiber_barrier, fiber_wave_sync);                         \
   } while (0)
       if (c.form == TileForm::WL_HALF) EMU_WL_RUN(11, false);
       else if (logr == 10) EMU_WL_RUN(10, true);
@@ -144,13 +201,16 @@ static void run_block(u32 T) {
     makecontext(&g_ctx[t], (void (*)())fiber_main, 1, (int)t);
     g_done[t] = 0;
   }
+  census_reset(T);
   for (;;) {
     bool any = false;
     for (u32 t = 0; t < T; t++) {
       if (g_done[t]) continue;
       any = true;
       g_cur = (int)t;
+      census_enter((int)t);
       swapcontext(&g_sched, &g_ctx[t]);
+      census_leave();
     }
     if (!any) break;
   }
@@ -181,9 +241,10 @@ static u64 rnd_elem(u64& s) {   // uniform by rejection for primes near 2^64 (SU
 }
 
 static int g_dist_cfg = 0, g_dist_generic = 0;   // passes of the dist mode that ran a specialised / the generic body
-static void run_plan(const PlanDesc& pd, bool inv, const u64* in, u64* out, u64* tmp) {
+static void run_plan(const PlanDesc& pd, bool inv, const u64* in, u64* out, u64* tmp, int census_base = 0) {
   std::vector<u64> lds;
   for (auto& p : pd.passes) {
+    census_set_pass(census_base + (int)(&p - pd.passes.data()));
     TileArgs a = p.args;
     const u64* bufs_in[3] = {in, out, tmp};
     u64* bufs_out[3] = {nullptr, out, tmp};
@@ -206,6 +267,7 @@ static int dist_main(int log2n, int world, bool inv, int chunks) {
   std::vector<u64> x(n), ref(n), got(n);
   u64 s = 0x5EED0005ull + log2n;
   for (auto& v : x) v = rnd_elem(s);
+  load_words("RONK_EMU_INPUT", x.data(), n);
   std::vector<std::vector<u64>> loc(world), snd(world), rcv(world), res(world), tmp(world);
   for (int g = 0; g < world; g++) {
     loc[g].resize(per); snd[g].assign(per, 1); rcv[g].resize(per); res[g].assign(per, 2); tmp[g].assign(per, 3);
@@ -214,7 +276,7 @@ static int dist_main(int log2n, int world, bool inv, int chunks) {
     for (int j = 0; j < chunks; j++) {
       PlanDesc p1 = build_dist_phase1(log2n, inv, g, world, 4, g_twf, j, chunks, g_hf);
       if (p1.passes.empty()) { printf("no phase-1 plan\n"); return 2; }
-      run_plan(p1, inv, loc[g].data() + (u64)j * Cwc, snd[g].data() + (u64)j * sh.R * Cwc, tmp[g].data());
+      run_plan(p1, inv, loc[g].data() + (u64)j * Cwc, snd[g].data() + (u64)j * sh.R * Cwc, tmp[g].data(), 0);
     }
   }
   const u64 blk = sh.Rw * Cwc;   // one (source rank, chunk) block on the receiver
@@ -225,7 +287,7 @@ static int dist_main(int log2n, int world, bool inv, int chunks) {
   for (int h = 0; h < world; h++) {
     PlanDesc p2 = build_dist_phase2(log2n, inv, h, world, 4, g_twf, chunks, g_hf);
     if (p2.passes.empty()) { printf("no phase-2 plan\n"); return 2; }
-    run_plan(p2, inv, rcv[h].data(), res[h].data(), tmp[h].data());
+    run_plan(p2, inv, rcv[h].data(), res[h].data(), tmp[h].data(), 8);   // census: phase 2's passes count from 8
     for (u64 k2 = 0; k2 < sh.C; k2++)
       for (u64 k1l = 0; k1l < sh.Rw; k1l++) got[(h * sh.Rw + k1l) + sh.R * k2] = res[h][k2 * sh.Rw + k1l];
   }
@@ -234,6 +296,7 @@ static int dist_main(int log2n, int world, bool inv, int chunks) {
   for (u64 i = 0; i < n; i++)
     if (got[i] != ref[i]) { printf("DIST MISMATCH at %llu\n", (unsigned long long)i); return 1; }
   printf("passes: specialised=%d generic=%d\n", g_dist_cfg, g_dist_generic);
+  census_print();
   printf("OK dist log2n=%d world=%d inv=%d chunks=%d\n", log2n, world, (int)inv, chunks);
   return 0;
 }
@@ -266,13 +329,16 @@ static void run_mid_block(u32 T) {
     makecontext(&g_ctx[t], (void (*)())mid_fiber, 1, (int)t);
     g_done[t] = 0;
   }
+  census_reset(T);
   for (;;) {
     bool any = false;
     for (u32 t = 0; t < T; t++) {
       if (g_done[t]) continue;
       any = true;
       g_cur = (int)t;
+      census_enter((int)t);
       swapcontext(&g_sched, &g_ctx[t]);
+      census_leave();
     }
     if (!any) break;
   }
@@ -298,16 +364,20 @@ static int mul_main(int log2n, u64 d, u64 d2, int logc, int inv_twf) {
   for (u64 i = 0; i < d; i++) ab[i] = rnd_elem(s);
   for (u64 i = 0; i < d2; i++) ab[n + i] = rnd_elem(s);
   ab[0] = g_p - 1; ab[n + d2 - 1] = g_p - 1;
+  load_words("RONK_EMU_INPUT", ab.data(), d);
+  load_words("RONK_EMU_INPUT2", ab.data() + n, d2);
   std::vector<u64> lds;
   {   // F1: column pass of the batch of two, padding limits d / d2
     TileArgs a = bind_pass(F, 0, ab.data(), nullptr, ftmp.data());
     a.in_valid = d; a.in_valid1 = d2;
+    census_set_pass(0);
     run_pass(F.passes[0], a, false, lds);
   }
   TileArgs fa = bind_pass(F, 1, nullptr, nullptr, ftmp.data()), ia = bind_pass(I, 0, nullptr, nullptr, itmp.data());
   const int kindi = ia.tw_full ? 3 : 1, logr = F.passes[1].logr;
   if (!mul_mid_matches(fa, ia, logr, (int)fa.logc, kindi)) { printf("passes do not fuse\n"); return 2; }
   lds.assign(F.passes[1].lds_bytes / 8 + 1, 0);
+  census_set_pass(1);
   for (u32 bid = 0; bid < fa.tiles; bid++) {
     g_mid = MidArgs{&fa, &ia, lds.data(), bid, logr, (int)fa.logc, kindi};
     run_mid_block(F.passes[1].block);
@@ -315,6 +385,7 @@ static int mul_main(int log2n, u64 d, u64 d2, int logc, int inv_twf) {
   {   // I2: the inverse's row pass, output truncated to d + d2 - 1 coefficients
     TileArgs a = bind_pass(I, 1, nullptr, out.data(), itmp.data());
     a.out_valid = m;
+    census_set_pass(2);
     run_pass(I.passes[1], a, true, lds);
   }
   // the oracle: NTT product of the zero-padded operands (the schoolbook Mul is O(d * d2); at these sizes the two agree by
@@ -328,6 +399,7 @@ static int mul_main(int log2n, u64 d, u64 d2, int logc, int inv_twf) {
     if (i >= m) { if (out[i] != 0xDEADBEEFull) { printf("store beyond the product at %llu\n", (unsigned long long)i); return 1; } continue; }
     if (out[i] != pr[i]) { printf("MUL MISMATCH at %llu: got %llu want %llu\n", (unsigned long long)i, (unsigned long long)out[i], (unsigned long long)pr[i]); return 1; }
   }
+  census_print();
   printf("OK mul log2n=%d d=%llu d2=%llu logc=%d inverse twiddles=%s\n", log2n, (unsigned long long)d, (unsigned long long)d2, logc,
          kindi == 3 ? "matrix" : "two-level");
   return 0;
@@ -370,9 +442,11 @@ int main(int argc, char** argv) {
   for (auto& v : in) v = rnd_elem(s);
   // adversarial corners
   if (len) { in[0] = g_p - 1; if (n > 1) in[n - 1] = g_p - 1; if (n > 2) in[1] = 0; }
+  if (len) load_words("RONK_EMU_INPUT", in.data(), len);
   if (with_in2 && len) {
     for (auto& v : in2) v = rnd_elem(s);
     in2[0] = g_p - 1; in2[n - 1] = 0;
+    load_words("RONK_EMU_INPUT2", in2.data(), len);
   }
   std::vector<u64> lds;
   for (auto& p : pd.passes) {
@@ -388,6 +462,7 @@ int main(int argc, char** argv) {
     if (in_valid && p.in_buf == BUF_IN) a.in_valid = in_valid;
     if (in_valid1 && p.in_buf == BUF_IN) a.in_valid1 = in_valid1;
     if (out_valid && p.out_buf == BUF_OUT) a.out_valid = out_valid;
+    census_set_pass((int)(&p - pd.passes.data()));
     const TileChoice c = select_only ? (p.small ? TileChoice{} : select_tile(a, p.logr, inv, p.grid, p.block, tile_env()))
                                      : run_pass(p, a, inv, lds);
     printf("pass logr=%d logc=%u tiles=%u nb1=%u nb2=%u grid=%u block=%u lds=%zu kernel=%s\n", p.logr, a.logc, a.tiles,
@@ -409,6 +484,7 @@ int main(int argc, char** argv) {
              (unsigned long long)ref[i]);
       return 1;
     }
+  census_print();
   printf("OK log2n=%d batch=%llu inv=%d\n", log2n, (unsigned long long)batch, (int)inv);
   return 0;
 }
