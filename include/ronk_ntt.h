@@ -805,6 +805,59 @@ int ronk_ext2_vec_mul_base(uint64_t p, uint64_t w, const uint64_t* a, const uint
 int ronk_ext2_vec_pow(uint64_t p, uint64_t w, const uint64_t* a, uint64_t e, uint64_t* out, size_t n);
 int ronk_ext2_vec_inv(uint64_t p, uint64_t w, const uint64_t* a, uint64_t* out, size_t n);
 
+/* ---- running products and sums, the permutation grand product and the logUp running sum: the accumulator columns a PLONK- or
+ *      STARK-style prover builds from challenges drawn after its first commitment.  The reference stops at the permutation
+ *      polynomials S_sigma1..3 (src/compiler/program.rs:146-226) and has no prover; the semantics are fixed here and restated on
+ *      Python integers in tests/accum_ref.py.  Field: any odd prime p < 2^64 (Goldilocks on its own arithmetic, every other on the
+ *      Montgomery policy); extension F_p[t] / (t^2 - w) as above, checked by ronk_ext2_check, arrays PLANAR [2][n] (with w = 7
+ *      over Goldilocks the product with w is a shift).  Inputs may be any 64-bit words and are reduced; outputs are canonical.
+ *        scans     o is * or +, its identity e is 1 or 0.  exclusive = 0: out[i] = a[0] o .. o a[i]; exclusive = 1: out[0] = e,
+ *                  out[i] = a[0] o .. o a[i-1].  *d_total (may be NULL; one element: one word, or two for the extension) receives
+ *                  a[0] o .. o a[n-1].  d_out == d_a is allowed.  Field arithmetic is exact: every blocking gives these words.
+ *        permutation product   wires a, ids and sigma: [W][N] base words, row-major; beta, gamma: extension elements, two words
+ *                  each in device memory (as ronk_fri_fold_dev takes beta).  num_i = prod_(c < W) (a_c[i] + beta id_c[i] + gamma),
+ *                  den_i = prod_(c < W) (a_c[i] + beta sigma_c[i] + gamma); Z[0] = 1, Z[i+1] = Z[i] num_i / den_i.  d_Z: planar
+ *                  [2][N], receives Z[0..N-1]; d_last (two words) receives Z[N]; whether Z[N] = 1 is the caller's check.  A row
+ *                  with den_i = 0 contributes the factor ZERO (as ronk_ext2_vec_inv_dev writes zero) and sets *d_status = 1;
+ *                  otherwise *d_status = 0 (required; written by the call).  The reference's labels are id_c[i] = (c + 1) omega^i
+ *                  (Cell::label); the caller supplies the arrays, so any injective labelling works.
+ *        logUp sum   values v: [C][N]; multiplicities m: [C][N] base words, d_mult == NULL means all ones, "-k" is the word p - k;
+ *                  alpha: an extension element in device memory.  S[0] = 0, S[i+1] = S[i] + sum_(c < C) m_c[i] / (alpha + v_c[i]).
+ *                  d_S: planar [2][N], receives S[0..N-1]; d_last receives S[N].  A zero denominator makes that term ZERO and sets
+ *                  *d_status = 1 (else 0).
+ *        workspace d_work: ronk_scan_workspace_words(n) words, caller-owned; 0 for n = 0 or n > 2^28.
+ *      Errors, all found before a device is needed: NULL pointer (d_total and d_mult excepted), n = 0, n_columns = 0 or exclusive
+ *      other than 0 or 1: RONK_ERR_INVALID; n > 2^28 or n_columns > 16: RONK_ERR_UNSUPPORTED; the codes of ronk_ext2_check (for the
+ *      base-field scans: p < 2 RONK_ERR_INVALID, p = 2 RONK_ERR_UNSUPPORTED, else ronk_check_prime).  ronk_accum_check (host-side
+ *      integer logic): the codes of ronk_ext2_check, then RONK_ERR_INVALID, then RONK_ERR_UNSUPPORTED as above.
+ *      Every _dev call is asynchronous on `stream`: three kernel launches, no workgroup ever waits for another, no host round
+ *      trip, no library workspace -- legal under stream capture.  Outputs must not overlap inputs, except the elementwise aliasing
+ *      of the plain scans. */
+size_t ronk_scan_workspace_words(size_t n);
+int ronk_vec_prefix_prod_dev(uint64_t p, const uint64_t* d_a, uint64_t* d_out, size_t n, int exclusive, uint64_t* d_total,
+                             uint64_t* d_work, void* stream);
+int ronk_vec_prefix_sum_dev(uint64_t p, const uint64_t* d_a, uint64_t* d_out, size_t n, int exclusive, uint64_t* d_total,
+                            uint64_t* d_work, void* stream);
+int ronk_ext2_vec_prefix_prod_dev(uint64_t p, uint64_t w, const uint64_t* d_a, uint64_t* d_out, size_t n, int exclusive,
+                                  uint64_t* d_total, uint64_t* d_work, void* stream);
+int ronk_ext2_vec_prefix_sum_dev(uint64_t p, uint64_t w, const uint64_t* d_a, uint64_t* d_out, size_t n, int exclusive,
+                                 uint64_t* d_total, uint64_t* d_work, void* stream);
+int ronk_accum_check(uint64_t p, uint64_t w, uint32_t n_columns, size_t n);
+int ronk_perm_product_dev(uint64_t p, uint64_t w, const uint64_t* d_wires, const uint64_t* d_ids, const uint64_t* d_sigma,
+                          uint32_t n_columns, size_t n, const uint64_t* d_beta, const uint64_t* d_gamma, uint64_t* d_Z, uint64_t* d_last,
+                          uint64_t* d_work, int* d_status, void* stream);
+int ronk_logup_sum_dev(uint64_t p, uint64_t w, const uint64_t* d_vals, const uint64_t* d_mult, uint32_t n_columns, size_t n,
+                       const uint64_t* d_alpha, uint64_t* d_S, uint64_t* d_last, uint64_t* d_work, int* d_status, void* stream);
+/* Host-pointer forms, synchronous; they allocate their own workspace.  `total` may be NULL; `status` is required. */
+int ronk_vec_prefix_prod(uint64_t p, const uint64_t* a, uint64_t* out, size_t n, int exclusive, uint64_t* total);
+int ronk_vec_prefix_sum(uint64_t p, const uint64_t* a, uint64_t* out, size_t n, int exclusive, uint64_t* total);
+int ronk_ext2_vec_prefix_prod(uint64_t p, uint64_t w, const uint64_t* a, uint64_t* out, size_t n, int exclusive, uint64_t* total);
+int ronk_ext2_vec_prefix_sum(uint64_t p, uint64_t w, const uint64_t* a, uint64_t* out, size_t n, int exclusive, uint64_t* total);
+int ronk_perm_product(uint64_t p, uint64_t w, const uint64_t* wires, const uint64_t* ids, const uint64_t* sigma, uint32_t n_columns,
+                      size_t n, const uint64_t* beta, const uint64_t* gamma, uint64_t* Z, uint64_t* last, int* status);
+int ronk_logup_sum(uint64_t p, uint64_t w, const uint64_t* vals, const uint64_t* mult, uint32_t n_columns, size_t n,
+                   const uint64_t* alpha, uint64_t* S, uint64_t* last, int* status);
+
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);
 int ronk_dev_free(void* ptr);

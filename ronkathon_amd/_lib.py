@@ -220,6 +220,20 @@ _SIG = {
     "ronk_ext2_vec_mul_base": (_int, [_u64, _u64, _vp, _vp, _vp, _sz]),
     "ronk_ext2_vec_pow": (_int, [_u64, _u64, _vp, _u64, _vp, _sz]),
     "ronk_ext2_vec_inv": (_int, [_u64, _u64, _vp, _vp, _sz]),
+    "ronk_scan_workspace_words": (_sz, [_sz]),
+    "ronk_vec_prefix_prod_dev": (_int, [_u64, _vp, _vp, _sz, _int, _vp, _vp, _vp]),
+    "ronk_vec_prefix_sum_dev": (_int, [_u64, _vp, _vp, _sz, _int, _vp, _vp, _vp]),
+    "ronk_ext2_vec_prefix_prod_dev": (_int, [_u64, _u64, _vp, _vp, _sz, _int, _vp, _vp, _vp]),
+    "ronk_ext2_vec_prefix_sum_dev": (_int, [_u64, _u64, _vp, _vp, _sz, _int, _vp, _vp, _vp]),
+    "ronk_accum_check": (_int, [_u64, _u64, C.c_uint32, _sz]),
+    "ronk_perm_product_dev": (_int, [_u64, _u64, _vp, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ronk_logup_sum_dev": (_int, [_u64, _u64, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ronk_vec_prefix_prod": (_int, [_u64, _vp, _vp, _sz, _int, _vp]),
+    "ronk_vec_prefix_sum": (_int, [_u64, _vp, _vp, _sz, _int, _vp]),
+    "ronk_ext2_vec_prefix_prod": (_int, [_u64, _u64, _vp, _vp, _sz, _int, _vp]),
+    "ronk_ext2_vec_prefix_sum": (_int, [_u64, _u64, _vp, _vp, _sz, _int, _vp]),
+    "ronk_perm_product": (_int, [_u64, _u64, _vp, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, _vp, C.POINTER(_int)]),
+    "ronk_logup_sum": (_int, [_u64, _u64, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, C.POINTER(_int)]),
     "ronk_dev_alloc": (_int, [C.POINTER(_vp), _sz]),
     "ronk_dev_free": (_int, [_vp]),
     "ronk_memcpy_h2d": (_int, [_vp, _vp, _sz]),

@@ -423,3 +423,70 @@ class FriPcs:
     def verify(self, root, z, seed, proof):
         """-> 0, or bits: 1 / 2 / 4 as FRI reports them, 8 a matrix path fails, 16 a DEEP mismatch, 32 a point on the domain"""
         return self.handle.verify(root, z, seed, proof)
+
+
+def _prefix(field, values, exclusive, w, base_fn, ext_fn):
+    p = field.ORDER
+    a = L.arr(values)
+    if a.size == 0 or (w is not None and a.size % 2):
+        raise L.RonkPanic(L.ERR_INVALID, "a scan takes at least one element; extension arrays are planar [2][n]")
+    out = np.empty_like(a)
+    if w is None:
+        total = np.zeros(1, dtype=np.uint64)
+        L.check(base_fn(p, L.ptr(a), L.ptr(out), a.size, int(bool(exclusive)), L.ptr(total)))
+        return out, int(total[0])
+    total = np.zeros(2, dtype=np.uint64)
+    L.check(ext_fn(p, w, L.ptr(a), L.ptr(out), a.size // 2, int(bool(exclusive)), L.ptr(total)))
+    return out, (int(total[0]), int(total[1]))
+
+
+def prefix_prod(field, values, exclusive=False, w=None):
+    """the running product of include/ronk_ntt.h ("running products and sums"): out[i] = a[0] .. a[i], or with exclusive
+    out[0] = 1 and out[i] = a[0] .. a[i-1]; -> (out, the product of all).  With w, a quadratic non-residue of the field, the
+    elements are pairs of F_p[t] / (t^2 - w) in planar [2][n] words and the total is a pair."""
+    return _prefix(field, values, exclusive, w, L.lib.ronk_vec_prefix_prod, L.lib.ronk_ext2_vec_prefix_prod)
+
+
+def prefix_sum(field, values, exclusive=False, w=None):
+    """the running sum, as prefix_prod"""
+    return _prefix(field, values, exclusive, w, L.lib.ronk_vec_prefix_sum, L.lib.ronk_ext2_vec_prefix_sum)
+
+
+def _columns(what, m, like=None):
+    m = np.ascontiguousarray(np.asarray(m, dtype=np.uint64))
+    if m.ndim != 2 or m.size == 0 or (like is not None and m.shape != like.shape):
+        raise L.RonkPanic(L.ERR_INVALID, "%s is [columns][n], the same shape for every input" % what)
+    return m
+
+
+def perm_product(field, w, wires, ids, sigma, beta, gamma):
+    """The permutation grand product over F_p[t] / (t^2 - w): wires, ids, sigma are [columns][n] base words, beta and gamma pairs.
+    -> (Z planar [2][n] with Z[0] = 1, Z[n] as a pair, status): Z[i+1] = Z[i] prod_c (a_c[i] + beta id_c[i] + gamma) /
+    prod_c (a_c[i] + beta sigma_c[i] + gamma); status 1 when a denominator was ZERO (that row contributes ZERO).  Whether
+    Z[n] = (1, 0) is the caller's check."""
+    a = _columns("wires", wires)
+    i, s = _columns("ids", ids, a), _columns("sigma", sigma, a)
+    b, g = L.arr([int(c) for c in beta]), L.arr([int(c) for c in gamma])
+    if b.size != 2 or g.size != 2:
+        raise L.RonkPanic(L.ERR_INVALID, "an extension challenge is a pair")
+    n = a.shape[1]
+    Z, last, st = np.empty(2 * n, dtype=np.uint64), np.zeros(2, dtype=np.uint64), C.c_int(-1)
+    L.check(L.lib.ronk_perm_product(field.ORDER, w, L.ptr(a), L.ptr(i), L.ptr(s), a.shape[0], n, L.ptr(b), L.ptr(g), L.ptr(Z), L.ptr(last),
+                                    C.byref(st)))
+    return Z, (int(last[0]), int(last[1])), st.value
+
+
+def logup_sum(field, w, vals, mult, alpha):
+    """The logUp running sum over F_p[t] / (t^2 - w): vals and mult are [columns][n] base words (mult None: all ones; "-k" is the
+    word p - k), alpha a pair.  -> (S planar [2][n] with S[0] = 0, S[n] as a pair, status): S[i+1] = S[i] + sum_c m_c[i] /
+    (alpha + v_c[i]); status 1 when a denominator was ZERO (that term is ZERO)."""
+    v = _columns("vals", vals)
+    m = None if mult is None else _columns("mult", mult, v)
+    al = L.arr([int(c) for c in alpha])
+    if al.size != 2:
+        raise L.RonkPanic(L.ERR_INVALID, "an extension challenge is a pair")
+    n = v.shape[1]
+    S, last, st = np.empty(2 * n, dtype=np.uint64), np.zeros(2, dtype=np.uint64), C.c_int(-1)
+    L.check(L.lib.ronk_logup_sum(field.ORDER, w, L.ptr(v), None if m is None else L.ptr(m), v.shape[0], n, L.ptr(al), L.ptr(S), L.ptr(last),
+                                 C.byref(st)))
+    return S, (int(last[0]), int(last[1])), st.value
