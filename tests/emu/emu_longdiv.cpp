@@ -18,6 +18,7 @@
 #include "../../oracle/ronk_oracle.h"
 #include "../../ronkathon_amd/csrc/gl64.h"
 #include "../../ronkathon_amd/csrc/longdiv_kernel.h"
+#include "../../ronkathon_amd/csrc/mont64.h"
 
 using namespace ronk;
 
@@ -33,7 +34,19 @@ struct GlHostOps {
   u64 pow(u64 a, u64 e) const { return gl64::pow(a, e); }
   u64 order() const { return gl64::P; }
 };
-struct ModOps {
+// every odd prime but Goldilocks: the host mirror of MontOps (csrc/field_kernels.h), that is mont64.h itself -- the portable branch
+// of its carry chains under g++, the device form (`__clang__`) under the HIP toolchain's clang++.  The expected values come from
+// the oracle's `__int128 % p`.
+struct MontHostOps {
+  mont64::Field f;
+  u64 add(u64 a, u64 b) const { return mont64::add(f, a, b); }
+  u64 sub(u64 a, u64 b) const { return mont64::sub(f, a, b); }
+  u64 mul(u64 a, u64 b) const { return mont64::mul(f, a, b); }
+  u64 neg(u64 a) const { return mont64::neg(f, a); }
+  u64 pow(u64 a, u64 e) const { return mont64::pow(f, a, e); }
+  u64 order() const { return f.p; }
+};
+struct ModOps {                                            // p = 2 (mont64 needs an odd modulus)
   u64 p;
   u64 sub(u64 a, u64 b) const { return a >= b ? a - b : a + (p - b); }
   u64 mul(u64 a, u64 b) const { return (u64)(((unsigned __int128)a * b) % p); }
@@ -63,6 +76,8 @@ static Job g_job;
 static void fiber_main(int tid) {
   FiberCtx cx{(size_t)tid, g_job.T, &g_job.top, &g_job.lead};
   if (g_job.gl) poly_divrem_body(GlHostOps(), g_job.a, g_job.rem, g_job.d, g_job.b, g_job.d2, g_job.quot, g_job.status, cx);
+  else if (g_job.p > 2 && (g_job.p & 1))
+    poly_divrem_body(MontHostOps{mont64::make_field(g_job.p)}, g_job.a, g_job.rem, g_job.d, g_job.b, g_job.d2, g_job.quot, g_job.status, cx);
   else poly_divrem_body(ModOps{g_job.p}, g_job.a, g_job.rem, g_job.d, g_job.b, g_job.d2, g_job.quot, g_job.status, cx);
   g_done[tid] = 1;
   swapcontext(&g_ctx[tid], &g_sched);

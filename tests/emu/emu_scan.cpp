@@ -17,6 +17,7 @@
 
 #include "../../oracle/ronk_oracle.h"
 #include "../../ronkathon_amd/csrc/lindiv_kernels.h"
+#include "../../ronkathon_amd/csrc/mont64.h"
 
 using namespace ronk;
 
@@ -31,7 +32,18 @@ struct GlHostOps {
   u64 add(u64 a, u64 b) const { return gl64::add(a, b); }
   u64 mul(u64 a, u64 b) const { return gl64::mul(a, b); }
 };
-struct ModOps {
+// every odd prime but Goldilocks: the host mirror of MontOps (csrc/field_kernels.h), that is mont64.h itself -- the portable branch
+// of its carry chains under g++, the device form (`__clang__`) under the HIP toolchain's clang++.  The expected values below stay
+// on the oracle's `__int128 % p`.
+struct MontHostOps {
+  mont64::Field f;
+  u64 add(u64 a, u64 b) const { return mont64::add(f, a, b); }
+  u64 sub(u64 a, u64 b) const { return mont64::sub(f, a, b); }
+  u64 mul(u64 a, u64 b) const { return mont64::mul(f, a, b); }
+  u64 neg(u64 a) const { return mont64::neg(f, a); }
+  u64 pow(u64 a, u64 e) const { return mont64::pow(f, a, e); }
+};
+struct ModOps {                                            // p = 2 (mont64 needs an odd modulus)
   u64 p;
   u64 add(u64 a, u64 b) const { return (u64)(((unsigned __int128)a + b) % p); }
   u64 mul(u64 a, u64 b) const { return (u64)(((unsigned __int128)a * b) % p); }
@@ -103,7 +115,9 @@ static void run_item_ops(const Ops& ops, u32 tid) {
   if (g_job.direct) run_item<LINDIV_DLOAD>(ops, tid); else run_item<0>(ops, tid);
 }
 static void fiber_main(int tid) {
-  if (g_job.gl) run_item_ops(GlHostOps(), (u32)tid); else run_item_ops(ModOps{g_job.p}, (u32)tid);
+  if (g_job.gl) run_item_ops(GlHostOps(), (u32)tid);
+  else if (g_job.p > 2 && (g_job.p & 1)) run_item_ops(MontHostOps{mont64::make_field(g_job.p)}, (u32)tid);
+  else run_item_ops(ModOps{g_job.p}, (u32)tid);
   g_done[tid] = 1;
   swapcontext(&g_ctx[tid], &g_sched);
 }

@@ -1,6 +1,8 @@
 """Run by tests/test_gpu_parity.py::test_scan_onepass_variants in a fresh process (the library reads its RONK_* knobs
 once): evaluate and division by a linear factor through the device API against the oracle, repeated calls with
-different sizes (the one-launch forms alternate between two look-back arrays that the PREVIOUS call cleared)."""
+different sizes (the one-launch forms alternate between two look-back arrays that the PREVIOUS call cleared).  Over Goldilocks,
+F_101 and the prime classes of tests/prime_classes.py (P_MID: both terms of mont64::add's select in every launch; P_62: no sum
+carries; MONT_P: every reduction by the carry), so that each env variant runs its MontOps instantiation over them too."""
 import os
 import sys
 
@@ -15,6 +17,7 @@ def main():
     import torch
 
     import oracle as orc
+    import prime_classes as PC
     from ronkathon_amd import _lib as L
     from conftest import splitmix_field
     GP = 0xFFFFFFFF00000001
@@ -22,7 +25,7 @@ def main():
     torch.zeros(1).cuda()
     side = torch.cuda.Stream()
     sizes = [(1 << 20) + 77, 5, 2048, 2049, (1 << 22), 40000, (1 << 23) - 3, 4096 * 3 + 5, 1 << 21]
-    for p in (GP, 101):
+    for p in (GP, 101, PC.P_MID, PC.P_62, PC.MONT_P):
         for rep, d in enumerate(sizes if p == GP else sizes[:4] + [70001]):
             a = splitmix_field(100 + rep, d, p)
             da = torch.from_numpy(a.view(np.int64)).cuda()

@@ -384,7 +384,7 @@ SCAN_EXE = os.path.join(ROOT, "build", "emu_scan")
 def emu_scan():
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     src = os.path.join(ROOT, "tests", "emu", "emu_scan.cpp")
-    deps = [src] + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("lindiv_kernels.h", "gl64.h")]
+    deps = [src] + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("lindiv_kernels.h", "gl64.h", "mont64.h")]
     if not os.path.exists(SCAN_EXE) or any(os.path.getmtime(d) > os.path.getmtime(SCAN_EXE) for d in deps):
         obj = os.path.join(ROOT, "build", "orc_emu.o")
         _build(["gcc", "-O2", "-c", "-o", obj, os.path.join(ROOT, "oracle", "ronk_oracle.c")], obj)
@@ -434,6 +434,55 @@ def test_one_launch_linear_division_on_fibers(emu_scan, mode, pl):
         run(emu_scan, GP, 4096 * pl // 4 * 601 + 5, 987654321987, 3, mode, 5, env=env)   # 601 chunks
 
 
+# ---- the same bodies over the prime classes (tests/prime_classes.py), on the product's own mont64.h in both compile forms.
+# emu_scan / emu_longdiv give every odd prime but Goldilocks a host mirror of MontOps (mont64::add / sub / mul / pow on
+# mont64::make_field(p)); the expected values stay on the oracle's `__int128 % p`.  g++ compiles mont64.h's portable branch, the HIP
+# toolchain's clang++ the carry-chain branch that the device build compiles.
+CLASS_PRIMES = [PC.P_MID, PC.P_62, PC.MONT_P]
+CLASS_IDS = ["P_MID", "P_62", "MONT_P"]
+Z_RANDOM = 0x9E3779B97F4A7C15           # reduced mod p by the emulator
+
+
+@pytest.fixture(scope="module")
+def emu_scan_device_form(emu_scan):
+    src = os.path.join(ROOT, "tests", "emu", "emu_scan.cpp")
+    deps = [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("lindiv_kernels.h", "gl64.h", "mont64.h")]
+    return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_scan_clang"), [src, os.path.join(ROOT, "build", "orc_emu.o")], deps, "-O2")
+
+
+@pytest.mark.parametrize("p", CLASS_PRIMES, ids=CLASS_IDS)
+@pytest.mark.parametrize("form", ["portable", "device"])
+def test_two_launch_linear_division_over_the_prime_classes(request, form, p):
+    """lindiv_scan_body / lindiv_apply_body with mont64.h as their arithmetic: through the LDS image and with 16-byte direct loads,
+    one coefficient .. 35 chunks, the chunk edge, z = 0 / 1 / p - 1 / random, a non-monic divisor"""
+    exe = request.getfixturevalue("emu_scan" if form == "portable" else "emu_scan_device_form")
+    for direct in (0, 1):
+        for d in (1, 513, 4095, 4097, 70001):
+            run(exe, p, d, Z_RANDOM, 1, direct)
+        for z in (0, 1, p - 1):
+            run(exe, p, 9000, z, 1, direct)
+        run(exe, p, 9000, Z_RANDOM, p - 1, direct)
+        run(exe, p, 4097, 0, 5, direct)
+
+
+@pytest.mark.parametrize("p", CLASS_PRIMES, ids=CLASS_IDS)
+@pytest.mark.parametrize("pl", [4, 8])
+@pytest.mark.parametrize("mode", [2, 3, 6])
+@pytest.mark.parametrize("form", ["portable", "device"])
+def test_one_launch_linear_division_over_the_prime_classes(request, form, mode, pl, p):
+    """lindiv_one_body with mont64.h as its arithmetic: through the LDS image, with direct loads, and with every look-back wait
+    failing; 4 and 8 coefficients per lane; one coefficient, a wavefront edge, both sides of the first chunk edge, several chunks;
+    z = 1 / p - 1 / random, non-monic divisors"""
+    exe = request.getfixturevalue("emu_scan" if form == "portable" else "emu_scan_device_form")
+    env = {"EMU_LINDIV1_PL": str(pl)}
+    for d in (1, 513, 4096 * pl // 4 - 1, 4096 * pl // 4 + 1, 70001):
+        run(exe, p, d, Z_RANDOM, 1, mode, env=env)
+    for z in (1, p - 1):
+        run(exe, p, 9000, z, 1, mode, env=env)
+    run(exe, p, 9000, Z_RANDOM, p - 1, mode, env=env)
+    run(exe, p, 4096 * pl // 4 + 1, 1, 5, mode, env=env)
+
+
 # ---- the long-division kernel (ronkathon_amd/csrc/longdiv_kernel.h) on fibers: tests/emu/emu_longdiv.cpp
 LONGDIV_EXE = os.path.join(ROOT, "build", "emu_longdiv")
 
@@ -442,7 +491,7 @@ LONGDIV_EXE = os.path.join(ROOT, "build", "emu_longdiv")
 def emu_longdiv():
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     src = os.path.join(ROOT, "tests", "emu", "emu_longdiv.cpp")
-    deps = [src] + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("longdiv_kernel.h", "gl64.h")] + \
+    deps = [src] + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("longdiv_kernel.h", "gl64.h", "mont64.h")] + \
            [os.path.join(ROOT, "oracle", "ronk_oracle.c")]
     if not os.path.exists(LONGDIV_EXE) or any(os.path.getmtime(d) > os.path.getmtime(LONGDIV_EXE) for d in deps):
         obj = os.path.join(ROOT, "build", "orc_emu_longdiv.o")
@@ -463,6 +512,26 @@ def test_long_division_kernel_on_fibers(emu_longdiv):
         out = subprocess.run([emu_longdiv, hex(p), str(cases), str(maxd), str(items), str(seed)], capture_output=True, text=True,
                              timeout=600)
         assert out.returncode == 0 and out.stdout.startswith("OK"), (p, out.stdout[-300:])
+
+
+@pytest.fixture(scope="module")
+def emu_longdiv_device_form(emu_longdiv):
+    src = os.path.join(ROOT, "tests", "emu", "emu_longdiv.cpp")
+    deps = [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("longdiv_kernel.h", "gl64.h", "mont64.h")]
+    return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_longdiv_clang"), [src, os.path.join(ROOT, "build", "orc_emu_longdiv.o")],
+                                     deps, "-O2")
+
+
+@pytest.mark.parametrize("p", CLASS_PRIMES, ids=CLASS_IDS)
+@pytest.mark.parametrize("form", ["portable", "device"])
+def test_long_division_kernel_over_the_prime_classes(request, form, p):
+    """poly_divrem_body with mont64.h as its arithmetic (the inverse of the leading coefficient by mont64::pow, the elimination by
+    mont64::sub / mul), value for value and panic for panic against orc_poly_divrem: fewer cases of the shapes that Goldilocks
+    gets above (64, 256, 1024 and one work-item; ragged divisors, reference panics, in place)"""
+    exe = request.getfixturevalue("emu_longdiv" if form == "portable" else "emu_longdiv_device_form")
+    for cases, maxd, items, seed in ((150, 200, 64, 3), (4, 1500, 256, 9), (12, 90, 1024, 5), (100, 50, 1, 4)):
+        out = subprocess.run([exe, hex(p), str(cases), str(maxd), str(items), str(seed)], capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0 and out.stdout.startswith("OK"), (hex(p), out.stdout[-300:])
 
 
 @pytest.mark.parametrize("args", [(20, 1, 1, 3), (19, 2, 1, 4, 18), (18, 1, 0, 4, 18), (21, 1, 0, 2, 21)])

@@ -27,6 +27,7 @@ import torch  # noqa: E402
 
 import oracle as orc  # noqa: E402
 import ronkathon_amd as R  # noqa: E402
+import prime_classes as PC  # noqa: E402
 from conftest import splitmix_field  # noqa: E402
 from ronkathon_amd import _lib as L  # noqa: E402
 
@@ -285,8 +286,9 @@ def sec_divrem(deadline):
     it = 0
     while time.time() < deadline:
         it += 1
-        p = rng.choice([GP, GP, 101, 17, 0xFFFFFFFFFFFFFFC5, 0xFFFFFFFC00000001, 29 * 2**57 + 1])   # (the last two: Newton over Montgomery)
-        big = p in (GP, 0xFFFFFFFC00000001, 29 * 2**57 + 1) and rng.random() < 0.25
+        # (the last three: Newton over Montgomery; P_MID takes both terms of mont64::add's select, tests/prime_classes.py)
+        p = rng.choice([GP, GP, 101, 17, 0xFFFFFFFFFFFFFFC5, PC.MONT_P, PC.P_62, PC.P_MID])
+        big = p in (GP, PC.MONT_P, PC.P_62, PC.P_MID) and rng.random() < 0.25
         d = rng.randrange(1, 40000 if big else 700)
         d2 = rng.randrange(1, d + 3)
         a = edge_values(p, d, 2 * it); b = edge_values(p, d2, 2 * it + 1)
@@ -363,7 +365,7 @@ def sec_lindiv(deadline):
     it = 0
     while time.time() < deadline:
         it += 1
-        p = rng.choice([GP, GP, GP, 101, 2, 0xFFFFFFFFFFFFFFC5])
+        p = rng.choice([GP, GP, GP, 101, 2, 0xFFFFFFFFFFFFFFC5, PC.P_MID, PC.P_62])
         d = rng.choice([rng.randrange(1, 64), rng.randrange(1, 5000), rng.randrange(1, 400000),
                         2048 * rng.randrange(1, 40) + rng.choice([-1, 0, 1]), rng.randrange(1, 1 << 23),
                         8192 * rng.randrange(129, 513) + rng.choice([-1, 0, 1])])   # (the one-launch form: 129 .. 512 chunks of 8192)
@@ -397,10 +399,12 @@ def sec_codes(deadline):
     it = 0
     while time.time() < deadline:
         it += 1
-        p = rng.choice([GP, GP, 101, 12289])
-        g = GG if p == GP else orc.find_primitive_element(p)
+        p = rng.choice([GP, GP, 101, 12289, PC.P_MID, PC.P_62])
+        g = GG if p == GP else PC.GEN[p] if p in PC.GEN else orc.find_primitive_element(p)
         if p == GP:
             logn = rng.randrange(1, 15 if rng.random() < 0.8 else 21)
+        elif p in PC.BY_P:                           # any size the 2-adicity allows; k stays at most 600 below (the O(K^2) decode)
+            logn = rng.randrange(1, min(PC.BY_P[p].two_adicity, 14) + 1)
         else:
             logn = rng.randrange(1, {101: 3, 12289: 13}[p])
         n = 1 << logn
@@ -458,7 +462,7 @@ def sec_vec(deadline):
     it = 0
     while time.time() < deadline:
         it += 1
-        p = rng.choice([GP, GP, 101, 2, 3, 0xFFFFFFFFFFFFFFC5, 0x7FFFFFFF])
+        p = rng.choice([GP, GP, 101, 2, 3, 0xFFFFFFFFFFFFFFC5, 0x7FFFFFFF, PC.P_MID, PC.P_62])
         n = rng.choice([rng.randrange(1, 100), rng.randrange(1, 100000)])
         a = edge_values(p, n, 2 * it); b = edge_values(p, n, 2 * it + 1)
         out = np.empty(n, dtype=np.uint64)
@@ -503,11 +507,12 @@ def sec_lagrange(deadline):
     it = 0
     while time.time() < deadline:
         it += 1
-        p = rng.choice([GP, GP, 101, 12289])
-        g = GG if p == GP else orc.find_primitive_element(p)
+        p = rng.choice([GP, GP, 101, 12289, PC.P_MID, PC.P_62])
+        g = GG if p == GP else PC.GEN[p] if p in PC.GEN else orc.find_primitive_element(p)
         if rng.random() < 0.6:   # Lagrange::new's node table, any n | p - 1
             n = rng.choice({GP: [2, 3, 5, 15, 16, 17, 256, 4096, 65536, 1 << 18, 3 << 16], 101: [2, 4, 5, 10, 25, 100],
-                            12289: [3, 4, 12, 256, 4096]}[p])
+                            12289: [3, 4, 12, 256, 4096], PC.P_MID: [2, 3, 16, 768, 4096, 65536, 1 << 18],
+                            PC.P_62: [2, 29, 16, 464, 4096, 65536, 1 << 18]}[p])
             nodes = orc.lagrange_nodes(p, g, n) if n & (n - 1) == 0 else None
             if nodes is None:
                 w = orc.primitive_root_of_unity(p, g, n)
