@@ -858,6 +858,42 @@ int ronk_perm_product(uint64_t p, uint64_t w, const uint64_t* wires, const uint6
 int ronk_logup_sum(uint64_t p, uint64_t w, const uint64_t* vals, const uint64_t* mult, uint32_t n_columns, size_t n,
                    const uint64_t* alpha, uint64_t* S, uint64_t* last, int* status);
 
+/* ---- PLONK quotient: the quotient polynomial of a three-wire PLONK circuit on the evaluation coset, in ONE kernel launch.  The
+ *      gate equation is the reference's a QL + b QR + a b QM + o QO + QC = 0 (src/compiler/program.rs:4-5,
+ *      CommonPreprocessedInput); the reference has no prover, so the semantics are fixed here and restated on Python integers in
+ *      tests/plonk_ref.py.  Field and extension as for the accumulators above (Goldilocks on its own arithmetic, every other odd
+ *      prime on the Montgomery policy; planar [2][M] extension arrays).
+ *        domain    N = 2^log2_n trace rows, B = 2^log2_blowup, M = N B; w_M = ronk_root_of_unity(p, g, M), w_N = w_M^B;
+ *                  x_i = s w_M^i, i < M, natural order, s = coset_shift: what ronk_lde_batch_dev leaves behind.
+ *        inputs    all on the coset, any 64-bit words (reduced): d_wires [3][M] = a, b, o; d_sel [5][M] = ql, qr, qm, qo, qc;
+ *                  d_sigma [3][M]; d_pi [M] or NULL for zero; d_Z planar [2][M], each plane the extension of one plane of what
+ *                  ronk_perm_product_dev wrote; alpha, beta, gamma: two words each in device memory.  The label multipliers
+ *                  k[0..2] are base words fixed at creation (the reference uses 1, 2, 3, Cell::label): the identity label of
+ *                  wire c at x is k_c x, generated in the kernel.  That the cosets k_c <w_N> are disjoint is the caller's concern.
+ *        row i     G  = a ql + b qr + a b qm + o qo + qc + pi
+ *                  P1 = Z_i prod_c (w_c + beta k_c x_i + gamma) - Z_((i + B) mod M) prod_c (w_c + beta sigma_c + gamma)
+ *                  P2 = (Z_i - 1) L1(x_i),  L1(x) = (x^N - 1) / (N (x - 1))
+ *                  T_i = (G + alpha P1 + alpha^2 P2) / (x_i^N - 1)
+ *        output    d_T planar [2][M], canonical.  It must not overlap any input: row i reads Z at row i + B.
+ *      ronk_plonk_check (host-side integer logic), in this order: the codes of ronk_ext2_check; RONK_ERR_INVALID for k == NULL,
+ *      s = 0 or some k_c = 0 (mod p); RONK_ERR_NO_ROOT when M does not divide p - 1; RONK_ERR_UNSUPPORTED for log2_n < 1,
+ *      log2(M) > 28 or s^M = 1 -- exactly the case where some x_i^N - 1 or x_i - 1 vanishes, so no division by zero is left and
+ *      there is no status word.  Whether g has the full power-of-two order is the caller's concern, as with ronk_root_of_unity.
+ *      The handle owns the two-level point table, the B values 1 / (x^N - 1), 1 / N and the k_c.  NULL pointers (d_pi excepted)
+ *      are RONK_ERR_INVALID before any device work.  The _dev call is asynchronous on `stream`: one kernel launch, no library
+ *      workspace, no host round trip -- legal under stream capture.  The host-pointer form is synchronous. */
+typedef struct ronk_plonk ronk_plonk;
+int ronk_plonk_check(uint64_t p, uint64_t g, uint64_t w, uint32_t log2_n, uint32_t log2_blowup, uint64_t coset_shift,
+                     const uint64_t k[3]);
+int ronk_plonk_create(ronk_plonk** out, uint64_t p, uint64_t g, uint64_t w, uint32_t log2_n, uint32_t log2_blowup,
+                      uint64_t coset_shift, const uint64_t k[3]);
+int ronk_plonk_destroy(ronk_plonk* h);
+int ronk_plonk_quotient_dev(const ronk_plonk* h, const uint64_t* d_wires, const uint64_t* d_sel, const uint64_t* d_sigma,
+                            const uint64_t* d_pi, const uint64_t* d_Z, const uint64_t* d_alpha, const uint64_t* d_beta,
+                            const uint64_t* d_gamma, uint64_t* d_T, void* stream);
+int ronk_plonk_quotient(const ronk_plonk* h, const uint64_t* wires, const uint64_t* sel, const uint64_t* sigma, const uint64_t* pi,
+                        const uint64_t* Z, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, uint64_t* T);
+
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);
 int ronk_dev_free(void* ptr);

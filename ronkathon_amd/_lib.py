@@ -234,6 +234,11 @@ _SIG = {
     "ronk_ext2_vec_prefix_sum": (_int, [_u64, _u64, _vp, _vp, _sz, _int, _vp]),
     "ronk_perm_product": (_int, [_u64, _u64, _vp, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, _vp, C.POINTER(_int)]),
     "ronk_logup_sum": (_int, [_u64, _u64, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, C.POINTER(_int)]),
+    "ronk_plonk_check": (_int, [_u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
+    "ronk_plonk_create": (_int, [C.POINTER(_vp), _u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
+    "ronk_plonk_destroy": (_int, [_vp]),
+    "ronk_plonk_quotient_dev": (_int, [_vp] * 11),
+    "ronk_plonk_quotient": (_int, [_vp] * 10),
     "ronk_dev_alloc": (_int, [C.POINTER(_vp), _sz]),
     "ronk_dev_free": (_int, [_vp]),
     "ronk_memcpy_h2d": (_int, [_vp, _vp, _sz]),

@@ -490,3 +490,26 @@ def logup_sum(field, w, vals, mult, alpha):
     L.check(L.lib.ronk_logup_sum(field.ORDER, w, L.ptr(v), None if m is None else L.ptr(m), v.shape[0], n, L.ptr(al), L.ptr(S), L.ptr(last),
                                  C.byref(st)))
     return S, (int(last[0]), int(last[1])), st.value
+
+
+def plonk_quotient(field, g, w, log2_n, log2_blowup, coset_shift, wires, sel, sigma, pi, Z, alpha, beta, gamma, k=(1, 2, 3)):
+    """The PLONK quotient on the coset x_i = coset_shift * w_M^i, M = 2^(log2_n + log2_blowup): wires [3][M], sel [5][M] (ql, qr, qm,
+    qo, qc), sigma [3][M], pi [M] or None, Z planar [2][M], all on the coset; alpha, beta, gamma pairs; k the label multipliers.
+    -> T planar [2][M]: (gate + alpha P1 + alpha^2 P2) / (x^N - 1) row by row (include/ronk_ntt.h "PLONK quotient")."""
+    M = 1 << (log2_n + log2_blowup)
+    cols = [_columns(name, m) for name, m in (("wires", wires), ("sel", sel), ("sigma", sigma), ("Z", Z))]
+    if [c.shape for c in cols] != [(3, M), (5, M), (3, M), (2, M)]:
+        raise L.RonkPanic(L.ERR_INVALID, "wires [3][M], sel [5][M], sigma [3][M], Z [2][M]")
+    p_i = None if pi is None else L.arr(pi)
+    ch = [L.arr([int(c) for c in e]) for e in (alpha, beta, gamma)]
+    if any(e.size != 2 for e in ch) or (p_i is not None and p_i.size != M) or len(k) != 3:
+        raise L.RonkPanic(L.ERR_INVALID, "an extension challenge is a pair, pi holds M words, k three")
+    h = C.c_void_p()
+    L.check(L.lib.ronk_plonk_create(C.byref(h), field.ORDER, g, w, log2_n, log2_blowup, coset_shift, (C.c_uint64 * 3)(*[int(v) for v in k])))
+    try:
+        T = np.empty(2 * M, dtype=np.uint64)
+        L.check(L.lib.ronk_plonk_quotient(h, L.ptr(cols[0]), L.ptr(cols[1]), L.ptr(cols[2]), None if p_i is None else L.ptr(p_i),
+                                          L.ptr(cols[3]), L.ptr(ch[0]), L.ptr(ch[1]), L.ptr(ch[2]), L.ptr(T)))
+    finally:
+        L.lib.ronk_plonk_destroy(h)
+    return T
