@@ -1,10 +1,11 @@
 // ronk_accum.hip -- C ABI of libronk_ntt.so, part 12: running products and sums over the 64-bit fields and their quadratic
-// extension, the permutation grand product and the logUp running sum (csrc/accum_kernels.h; include/ronk_ntt.h "running
-// products and sums").  Three launches per call, no host round trip and no library workspace: every _dev
-// call is legal under stream capture.
+// extension, the permutation grand product and the logUp running sum (csrc/accum_kernels.h, csrc/ext2_launch.h;
+// include/ronk_ntt.h "running products and sums").  Three launches per call, no host round trip and no
+// library workspace: every _dev call is legal under stream capture.
 #include "runtime.h"
 #include "hip_launch.h"
 #include "accum_kernels.h"
+#include "ext2_launch.h"
 
 extern "C" size_t ronk_scan_workspace_words(size_t n) { return (size_t)acc_work_words(n); }
 
@@ -27,34 +28,11 @@ int scan_args(const void* a, const void* out, const void* work, size_t n, int ex
   if (n > ACC_MAX_N) return RONK_ERR_UNSUPPORTED;
   return RONK_OK;
 }
-
-// what a launch knows: the policy, its constants and W in register form (w = 0: a base-field call)
-struct AccCtx {
-  bool mont, w7;
-  FriConsts k;
-  u64 w;
-};
-AccCtx acc_ctx(u64 p, u64 w) {
-  AccCtx c;
-  c.mont = p != RONK_GOLDILOCKS_P;
-  c.w7 = !c.mont && w % p == 7;
-  c.k = ext2_host_consts(c.mont, p);
-  c.w = ext2_reg_form(c.mont, p, w);
-  return c;
-}
 }  // namespace
-
-// run the launch with FF bound to the policy of the context
-#define ACC_DISPATCH(c, ...)                                \
-  do {                                                      \
-    if ((c).mont) { typedef FriMont FF; __VA_ARGS__; }      \
-    else if ((c).w7) { typedef FriGlW7 FF; __VA_ARGS__; }   \
-    else { typedef FriGl FF; __VA_ARGS__; }                 \
-  } while (0)
 
 // phases 2 and 3 over `a` (phase 1 has left the blocks' totals in d_work); d_status NULL: no flags
 template <class O>
-static int scan_tail(const AccCtx& c, const u64* a, u64* out, size_t n, int exclusive, u64* d_total, u64* d_work, int* d_status,
+static int scan_tail(const Ext2Launch& c, const u64* a, u64* out, size_t n, int exclusive, u64* d_total, u64* d_work, int* d_status,
                      hipStream_t s) {
   const u64 B = acc_blocks(n);
   hipLaunchKernelGGL((acc_phase2_kernel<O>), dim3(1), dim3(ACC_LANES), 0, s, c.k, c.w, d_work, B, d_total, d_status);
@@ -63,7 +41,7 @@ static int scan_tail(const AccCtx& c, const u64* a, u64* out, size_t n, int excl
   return RONK_OK;
 }
 template <class O>
-static int scan_launch(const AccCtx& c, const u64* a, u64* out, size_t n, int exclusive, u64* d_total, u64* d_work, hipStream_t s) {
+static int scan_launch(const Ext2Launch& c, const u64* a, u64* out, size_t n, int exclusive, u64* d_total, u64* d_work, hipStream_t s) {
   hipLaunchKernelGGL((acc_phase1_kernel<O>), dim3((u32)acc_blocks(n)), dim3(ACC_LANES), 0, s, c.k, c.w, a, n, d_work);
   return scan_tail<O>(c, a, out, n, exclusive, d_total, d_work, nullptr, s);
 }
@@ -73,10 +51,9 @@ static int base_scan_dev(u64 p, const u64* a, u64* out, size_t n, int exclusive,
   RCHK(scan_args(a, out, d_work, n, exclusive));
   RCHK(base_check(p));
   RCHK(need_device());
-  const AccCtx c = acc_ctx(p, 0);
+  const Ext2Launch c = ext2_launch(p, 0);
   int rc = RONK_OK;
-  if (c.mont) rc = scan_launch<AccOp<AccWord<FriMont>, OP>>(c, a, out, n, exclusive, d_total, d_work, (hipStream_t)st);
-  else rc = scan_launch<AccOp<AccWord<FriGl>, OP>>(c, a, out, n, exclusive, d_total, d_work, (hipStream_t)st);
+  EXT2_DISPATCH2(c, rc = (scan_launch<AccOp<AccWord<FF>, OP>>(c, a, out, n, exclusive, d_total, d_work, (hipStream_t)st)));
   return rc;
 }
 template <int OP>
@@ -84,9 +61,9 @@ static int ext2_scan_dev(u64 p, u64 w, const u64* a, u64* out, size_t n, int exc
   RCHK(scan_args(a, out, d_work, n, exclusive));
   RCHK(ronk_ext2_check(p, w));
   RCHK(need_device());
-  const AccCtx c = acc_ctx(p, w);
+  const Ext2Launch c = ext2_launch(p, w);
   int rc = RONK_OK;
-  ACC_DISPATCH(c, rc = (scan_launch<AccOp<AccPair<FF>, OP>>(c, a, out, n, exclusive, d_total, d_work, (hipStream_t)st)));
+  EXT2_DISPATCH3(c, rc = (scan_launch<AccOp<AccPair<FF>, OP>>(c, a, out, n, exclusive, d_total, d_work, (hipStream_t)st)));
   return rc;
 }
 
@@ -114,10 +91,10 @@ extern "C" int ronk_perm_product_dev(uint64_t p, uint64_t w, const uint64_t* d_w
   if (!d_wires || !d_ids || !d_sigma || !d_beta || !d_gamma || !d_Z || !d_last || !d_work || !d_status) return RONK_ERR_INVALID;
   RCHK(ronk_accum_check(p, w, n_columns, n));
   RCHK(need_device());
-  const AccCtx c = acc_ctx(p, w);
+  const Ext2Launch c = ext2_launch(p, w);
   hipStream_t s = (hipStream_t)stream;
   int rc = RONK_OK;
-  ACC_DISPATCH(c, {
+  EXT2_DISPATCH3(c, {
     hipLaunchKernelGGL((acc_perm_terms_kernel<FF>), dim3((u32)acc_blocks(n)), dim3(ACC_LANES), 0, s, c.k, c.w, d_wires, d_ids, d_sigma,
                        n_columns, n, d_beta, d_gamma, d_Z, d_work);
     rc = (scan_tail<AccOp<AccPair<FF>, ACC_PROD>>(c, d_Z, d_Z, n, 1, d_last, d_work, d_status, s));
@@ -131,10 +108,10 @@ extern "C" int ronk_logup_sum_dev(uint64_t p, uint64_t w, const uint64_t* d_vals
   if (!d_vals || !d_alpha || !d_S || !d_last || !d_work || !d_status) return RONK_ERR_INVALID;
   RCHK(ronk_accum_check(p, w, n_columns, n));
   RCHK(need_device());
-  const AccCtx c = acc_ctx(p, w);
+  const Ext2Launch c = ext2_launch(p, w);
   hipStream_t s = (hipStream_t)stream;
   int rc = RONK_OK;
-  ACC_DISPATCH(c, {
+  EXT2_DISPATCH3(c, {
     hipLaunchKernelGGL((acc_logup_terms_kernel<FF>), dim3((u32)acc_blocks(n)), dim3(ACC_LANES), 0, s, c.k, c.w, d_vals, d_mult,
                        n_columns, n, d_alpha, d_S, d_work);
     rc = (scan_tail<AccOp<AccPair<FF>, ACC_SUM>>(c, d_S, d_S, n, 1, d_last, d_work, d_status, s));
@@ -143,33 +120,20 @@ extern "C" int ronk_logup_sum_dev(uint64_t p, uint64_t w, const uint64_t* d_vals
 }
 
 // ------------------------------------------------------------------------------------- host-pointer forms, synchronous
-namespace {
-struct HostIn {
-  const u64* h;
-  size_t words;
-  DevBuf d;
-  int up() {
-    RCHK(d.alloc(words * 8));
-    if (h && words) HIPCHK(hipMemcpy(d.p, h, words * 8, hipMemcpyHostToDevice));
-    return RONK_OK;
-  }
-};
-// `ew` words per element; the scan runs in place on the device copy
+// `ew` words per element; the scan runs in place on the device copy.  `check` is the field's code, reported after the arguments'.
 template <class Call>
-int scan_host(int check, int ew, const u64* a, u64* out, size_t n, int exclusive, u64* total, Call&& call) {
+static int scan_host(int check, int ew, const u64* a, u64* out, size_t n, int exclusive, u64* total, Call&& call) {
   if (!a || !out || n == 0 || (exclusive != 0 && exclusive != 1)) return RONK_ERR_INVALID;
   if (n > ACC_MAX_N) return RONK_ERR_UNSUPPORTED;
   RCHK(check);
   RCHK(need_device());
-  HostIn in{a, (size_t)ew * n};
-  DevBuf work, tot;
-  RCHK(in.up()); RCHK(work.alloc(acc_work_words(n) * 8)); RCHK(tot.alloc(16));
-  RCHK(call(in.d.u(), tot.u(), work.u()));
-  HIPCHK(hipMemcpy(out, in.d.p, (size_t)ew * n * 8, hipMemcpyDeviceToHost));
-  if (total) HIPCHK(hipMemcpy(total, tot.p, (size_t)ew * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  u64 *da = hc.in(a, (size_t)ew * n), *work = hc.out(acc_work_words(n)), *tot = hc.out(2);
+  RCHK(hc.rc);
+  RCHK(call(da, tot, work));
+  RCHK(hc.get(out, da, (size_t)ew * n * 8));
+  return total ? hc.get(total, tot, (size_t)ew * 8) : RONK_OK;
 }
-}  // namespace
 
 extern "C" int ronk_vec_prefix_prod(uint64_t p, const uint64_t* a, uint64_t* out, size_t n, int exclusive, uint64_t* total) {
   return scan_host(base_check(p), 1, a, out, n, exclusive, total,
@@ -190,12 +154,16 @@ extern "C" int ronk_ext2_vec_prefix_sum(uint64_t p, uint64_t w, const uint64_t* 
                    [&](u64* x, u64* t, u64* wk) { return ronk_ext2_vec_prefix_sum_dev(p, w, x, x, n, exclusive, t, wk, nullptr); });
 }
 
-// the outputs of an accumulator call back to the host: the column [2][n], the last value, the status
-static int accum_host_out(const DevBuf& col, const DevBuf& tail, u64* out, size_t n, u64* last, int* status) {
-  HIPCHK(hipMemcpy(out, col.p, 2 * n * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(last, tail.p, 16, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(status, (const char*)tail.p + 16, sizeof(int), hipMemcpyDeviceToHost));
-  return RONK_OK;
+// The host form of an accumulator: the column [2][n], the last value and the status come back.  tail: the last value, then the
+// status.  call(column, last, work, status) queues the _dev form.
+template <class Call>
+static int accum_host(HostCall& hc, u64* out, size_t n, u64* last, int* status, Call&& call) {
+  u64 *col = hc.out(2 * n), *tail = hc.out(3), *work = hc.out(acc_work_words(n));
+  RCHK(hc.rc);
+  RCHK(call(col, tail, work, (int*)(tail + 2)));
+  RCHK(hc.get(out, col, 2 * n * 8));
+  RCHK(hc.get(last, tail, 16));
+  return hc.get(status, tail + 2, sizeof(int));
 }
 
 extern "C" int ronk_perm_product(uint64_t p, uint64_t w, const uint64_t* wires, const uint64_t* ids, const uint64_t* sigma,
@@ -205,13 +173,11 @@ extern "C" int ronk_perm_product(uint64_t p, uint64_t w, const uint64_t* wires, 
   RCHK(ronk_accum_check(p, w, n_columns, n));
   RCHK(need_device());
   const size_t m = (size_t)n_columns * n;
-  HostIn a{wires, m}, i{ids, m}, s{sigma, m}, b{beta, 2}, g{gamma, 2};
-  DevBuf col, tail, work;   // tail: the last value, then the status
-  RCHK(a.up()); RCHK(i.up()); RCHK(s.up()); RCHK(b.up()); RCHK(g.up());
-  RCHK(col.alloc(2 * n * 8)); RCHK(tail.alloc(24)); RCHK(work.alloc(acc_work_words(n) * 8));
-  RCHK(ronk_perm_product_dev(p, w, a.d.u(), i.d.u(), s.d.u(), n_columns, n, b.d.u(), g.d.u(), col.u(), tail.u(), work.u(),
-                             (int*)((char*)tail.p + 16), nullptr));
-  return accum_host_out(col, tail, Z, n, last, status);
+  HostCall hc;
+  const u64 *a = hc.in(wires, m), *i = hc.in(ids, m), *s = hc.in(sigma, m), *b = hc.in(beta, 2), *g = hc.in(gamma, 2);
+  return accum_host(hc, Z, n, last, status, [&](u64* col, u64* tail, u64* work, int* st) {
+    return ronk_perm_product_dev(p, w, a, i, s, n_columns, n, b, g, col, tail, work, st, nullptr);
+  });
 }
 
 extern "C" int ronk_logup_sum(uint64_t p, uint64_t w, const uint64_t* vals, const uint64_t* mult, uint32_t n_columns, size_t n,
@@ -220,11 +186,9 @@ extern "C" int ronk_logup_sum(uint64_t p, uint64_t w, const uint64_t* vals, cons
   RCHK(ronk_accum_check(p, w, n_columns, n));
   RCHK(need_device());
   const size_t m = (size_t)n_columns * n;
-  HostIn v{vals, m}, mu{mult, mult ? m : 0}, al{alpha, 2};
-  DevBuf col, tail, work;
-  RCHK(v.up()); RCHK(mu.up()); RCHK(al.up());
-  RCHK(col.alloc(2 * n * 8)); RCHK(tail.alloc(24)); RCHK(work.alloc(acc_work_words(n) * 8));
-  RCHK(ronk_logup_sum_dev(p, w, v.d.u(), mult ? mu.d.u() : nullptr, n_columns, n, al.d.u(), col.u(), tail.u(), work.u(),
-                          (int*)((char*)tail.p + 16), nullptr));
-  return accum_host_out(col, tail, S, n, last, status);
+  HostCall hc;
+  const u64 *v = hc.in(vals, m), *mu = hc.in(mult, m), *al = hc.in(alpha, 2);   // mult is optional
+  return accum_host(hc, S, n, last, status, [&](u64* col, u64* tail, u64* work, int* st) {
+    return ronk_logup_sum_dev(p, w, v, mu, n_columns, n, al, col, tail, work, st, nullptr);
+  });
 }

@@ -1,10 +1,12 @@
 // ronk_fri.hip -- C ABI of libronk_ntt.so, part 9: the FRI prover and verifier over the 64-bit fields, on the Poseidon sponge
 // and Merkle commitment of ronk_hash.hip (csrc/fri_kernels.h), with base-field challenges
 // (ronk_fri_create) or challenges and folded layers in the quadratic extension (ronk_fri_create_ext).
+// The launch context and the policy dispatch are those of csrc/ext2_launch.h.
 #include "runtime.h"
 #include "hip_launch.h"
 #include "poseidon_handle.h"
 #include "fri_kernels.h"
+#include "ext2_launch.h"
 
 // ------------------------------------------------------------------------------------- handle
 struct ronk_fri {
@@ -12,10 +14,9 @@ struct ronk_fri {
   u64 p, g, shift;
   FriShape sh;
   u32 log2_blowup;
-  bool mont;                    // Montgomery policy (any prime, and Goldilocks under a root convention without shift roots)
-  FriConsts k;
-  u64 w_reg = 0;                // extension handles (sh.ext): W in register form
-  bool w7 = false;              // shift roots and W = 7: the product with W is a shift (FriGlW7)
+  // mont: any prime, and Goldilocks under a root convention without shift roots; w, w7 (shift roots and W = 7: the product with
+  // W is a shift, FriGlW7): extension handles (sh.ext) only
+  Ext2Launch c;
   std::vector<FriLayer> layers;   // host copy; the table pointers are device pointers
   u64* d_tab = nullptr;         // per layer lo, hi; then the final layer's w^-j
   const u64* d_wfin = nullptr;
@@ -36,26 +37,16 @@ struct FriSmall {
   }
 };
 
-#define FRI_DISPATCH_E(F, eta, ...)                                       \
-  do {                                                                    \
-    if ((eta) == 1) { constexpr int ETA = 1; typedef F FF; __VA_ARGS__; } \
-    else if ((eta) == 2) { constexpr int ETA = 2; typedef F FF; __VA_ARGS__; } \
-    else { constexpr int ETA = 3; typedef F FF; __VA_ARGS__; }            \
+#define FRI_DISPATCH_E(eta, ...)                            \
+  do {                                                      \
+    if ((eta) == 1) { constexpr int ETA = 1; __VA_ARGS__; } \
+    else if ((eta) == 2) { constexpr int ETA = 2; __VA_ARGS__; } \
+    else { constexpr int ETA = 3; __VA_ARGS__; }            \
   } while (0)
 // run the statement with FF and ETA bound to the handle's field policy and arity
-#define FRI_DISPATCH(h, ...)                                        \
-  do {                                                              \
-    if ((h)->mont) FRI_DISPATCH_E(FriMont, (h)->sh.eta, __VA_ARGS__); \
-    else FRI_DISPATCH_E(FriGl, (h)->sh.eta, __VA_ARGS__);           \
-  } while (0)
-
+#define FRI_DISPATCH(h, ...) EXT2_DISPATCH2((h)->c, FRI_DISPATCH_E((h)->sh.eta, __VA_ARGS__))
 // the same for the extension kernels, where Goldilocks with W = 7 has a policy of its own
-#define FRI_DISPATCH_X(h, ...)                                            \
-  do {                                                                    \
-    if ((h)->mont) FRI_DISPATCH_E(FriMont, (h)->sh.eta, __VA_ARGS__);     \
-    else if ((h)->w7) FRI_DISPATCH_E(FriGlW7, (h)->sh.eta, __VA_ARGS__);  \
-    else FRI_DISPATCH_E(FriGl, (h)->sh.eta, __VA_ARGS__);                 \
-  } while (0)
+#define FRI_DISPATCH_X(h, ...) EXT2_DISPATCH3((h)->c, FRI_DISPATCH_E((h)->sh.eta, __VA_ARGS__))
 
 // ------------------------------------------------------------------------------------- kernels
 // one lane per output: A loads at stride m (coalesced across lanes), one store
@@ -234,9 +225,8 @@ static int fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint
   h->pos = pos; h->p = pos->p; h->g = g % h->p; h->shift = coset_shift % h->p; h->log2_blowup = log2_blowup;
   fri_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, &h->sh, ext, input_ext);
   const FriShape& sh = h->sh;
-  h->mont = !fri_gl_shift_roots(h->p, h->g, sh.eta);
-  h->k = fri_host_consts(h->mont, h->p, h->g, sh.eta);
-  if (ext) { h->w_reg = ext2_reg_form(h->mont, h->p, w); h->w7 = !h->mont && w % h->p == 7; }
+  const bool mont = !fri_gl_shift_roots(h->p, h->g, sh.eta);
+  h->c = ext2_launch(mont, fri_host_consts(mont, h->p, h->g, sh.eta), h->p, ext ? w : 0);
   // tables: per layer lo then hi, then the final layer's roots
   std::vector<size_t> off(sh.layers + 1);
   size_t words = 0;
@@ -250,9 +240,9 @@ static int fri_create(ronk_fri** out, const ronk_poseidon* pos, uint64_t g, uint
   std::vector<u64> tab(words);
   for (u32 l = 0; l < sh.layers; l++) {
     const u32 kb = fri_kbits(sh.log2m(l));
-    fri_host_layer_table(h->mont, h->p, h->g, h->shift, sh, l, tab.data() + off[l], tab.data() + off[l] + ((size_t)1 << kb));
+    fri_host_layer_table(mont, h->p, h->g, h->shift, sh, l, tab.data() + off[l], tab.data() + off[l] + ((size_t)1 << kb));
   }
-  fri_host_final_table(h->mont, h->p, h->g, sh, tab.data() + off[sh.layers]);
+  fri_host_final_table(mont, h->p, h->g, sh, tab.data() + off[sh.layers]);
   int rc = upload(tab, &h->d_tab);
   if (rc != RONK_OK) { ronk_fri_destroy(h); return rc; }
   h->d_wfin = h->d_tab + off[sh.layers];
@@ -299,15 +289,15 @@ extern "C" int ronk_fri_fold_dev(const ronk_fri* h, uint32_t layer, const uint64
     // d_beta: two words; d_in: layer `layer` as the handle lays it out; d_out: planar [2][N_l / A]
     if (h->sh.vw(layer) == 2)
       FRI_DISPATCH_X(h, hipLaunchKernelGGL((fri_fold_ext_kernel<FF, ETA, true>), dim3(grid_for((size_t)1 << ly.log2m)), dim3(256), 0,
-                                         (hipStream_t)stream, h->k, h->w_reg, ly, d_in, d_beta, d_out));
+                                         (hipStream_t)stream, h->c.k, h->c.w, ly, d_in, d_beta, d_out));
     else
       FRI_DISPATCH_X(h, hipLaunchKernelGGL((fri_fold_ext_kernel<FF, ETA, false>), dim3(grid_for((size_t)1 << ly.log2m)), dim3(256), 0,
-                                         (hipStream_t)stream, h->k, h->w_reg, ly, d_in, d_beta, d_out));
+                                         (hipStream_t)stream, h->c.k, h->c.w, ly, d_in, d_beta, d_out));
     HIPCHK(hipGetLastError());
     return RONK_OK;
   }
   FRI_DISPATCH(h, hipLaunchKernelGGL((fri_fold_kernel<FF, ETA>), dim3(grid_for((size_t)1 << ly.log2m)), dim3(256), 0, (hipStream_t)stream,
-                                     h->k, ly, d_in, d_beta, d_out));
+                                     h->c.k, ly, d_in, d_beta, d_out));
   HIPCHK(hipGetLastError());
   return RONK_OK;
 }
@@ -364,12 +354,8 @@ extern "C" int ronk_fri_prove_dev(const ronk_fri* h, const uint64_t* d_evals, co
     const u64 m = (u64)1 << sh.log2m(l);
     RCHK(ronk_merkle_open_dev(trees[l], m, D, sm.idx + l * Q, Q, d_proof + sh.path_off(l), sm.st, stream));
     const u32 log2_leaf = sh.eta + (sh.vw(l) == 2);   // the 2 A words of a planar leaf are gathered at the same stride m
-    if (h->mont)
-      hipLaunchKernelGGL((fri_gather_kernel<FriMont>), dim3(grid_for(Q << log2_leaf)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l),
-                         log2_leaf, sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
-    else
-      hipLaunchKernelGGL((fri_gather_kernel<FriGl>), dim3(grid_for(Q << log2_leaf)), dim3(256), 0, s, h->k, vals[l], sh.log2m(l),
-                         log2_leaf, sm.idx + l * Q, Q, d_proof + sh.leaf_off(l));
+    EXT2_DISPATCH2(h->c, hipLaunchKernelGGL((fri_gather_kernel<FF>), dim3(grid_for(Q << log2_leaf)), dim3(256), 0, s, h->c.k, vals[l],
+                                            sh.log2m(l), log2_leaf, sm.idx + l * Q, Q, d_proof + sh.leaf_off(l)));
     HIPCHK(hipGetLastError());
   }
   return RONK_OK;
@@ -392,22 +378,22 @@ extern "C" int ronk_fri_verify_dev(const ronk_fri* h, const uint64_t* d_proof, c
                                 (u64)1 << sh.log2m(l), D, d_proof + l * D, ok + l * Q, stream));
   const u32 nl = (u32)sh.size(L), first = nl >> h->log2_blowup;
   if (sh.ext) {
-    FRI_DISPATCH_X(h, hipLaunchKernelGGL((fri_check_ext_kernel<FF, ETA>), dim3(grid_for(Q)), dim3(256), 0, s, h->k, h->w_reg, h->d_layers, L,
+    FRI_DISPATCH_X(h, hipLaunchKernelGGL((fri_check_ext_kernel<FF, ETA>), dim3(grid_for(Q)), dim3(256), 0, s, h->c.k, h->c.w, h->d_layers, L,
                                        Q, d_proof, (u64)(L * D), (u64)nl, sh.in_ext, sm.betas, sm.idx, ok, d_status));
     HIPCHK(hipGetLastError());
     if (first < nl) {
-      if (h->mont) hipLaunchKernelGGL((fri_final_ext_kernel<FriMont>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
-      else hipLaunchKernelGGL((fri_final_ext_kernel<FriGl>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
+      EXT2_DISPATCH2(h->c, hipLaunchKernelGGL((fri_final_ext_kernel<FF>), dim3(1), dim3(256), 0, s, h->c.k, h->d_wfin, d_final, nl, first,
+                                              d_status));
       HIPCHK(hipGetLastError());
     }
     return RONK_OK;
   }
-  FRI_DISPATCH(h, hipLaunchKernelGGL((fri_check_kernel<FF, ETA>), dim3(grid_for(Q)), dim3(256), 0, s, h->k, h->d_layers, L, Q, d_proof,
+  FRI_DISPATCH(h, hipLaunchKernelGGL((fri_check_kernel<FF, ETA>), dim3(grid_for(Q)), dim3(256), 0, s, h->c.k, h->d_layers, L, Q, d_proof,
                                      (u64)(L * D), sm.betas, sm.idx, ok, d_status));
   HIPCHK(hipGetLastError());
   if (first < nl) {
-    if (h->mont) hipLaunchKernelGGL((fri_final_kernel<FriMont>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
-    else hipLaunchKernelGGL((fri_final_kernel<FriGl>), dim3(1), dim3(256), 0, s, h->k, h->d_wfin, d_final, nl, first, d_status);
+    EXT2_DISPATCH2(h->c, hipLaunchKernelGGL((fri_final_kernel<FF>), dim3(1), dim3(256), 0, s, h->c.k, h->d_wfin, d_final, nl, first,
+                                            d_status));
     HIPCHK(hipGetLastError());
   }
   return RONK_OK;
@@ -434,24 +420,22 @@ extern "C" int ronk_fri_prove(const ronk_fri* h, const uint64_t* evals, const ui
   if (!h || !evals || !seed || !proof) return RONK_ERR_INVALID;
   RCHK(need_device());
   const FriShape& sh = h->sh;
-  DevBuf de, ds, dw, dp;
-  RCHK(de.alloc(sh.vw(0) * sh.size(0) * 8)); RCHK(ds.alloc(sh.d * 8)); RCHK(dw.alloc(sh.workspace_words() * 8)); RCHK(dp.alloc(sh.proof_words() * 8));
-  HIPCHK(hipMemcpy(de.p, evals, sh.vw(0) * sh.size(0) * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds.p, seed, sh.d * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_fri_prove_dev(h, de.u(), ds.u(), dw.u(), dp.u(), nullptr));
-  HIPCHK(hipMemcpy(proof, dp.p, sh.proof_words() * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64 *de = hc.in(evals, sh.vw(0) * sh.size(0)), *ds = hc.in(seed, sh.d);
+  u64 *dw = hc.out(sh.workspace_words()), *dp = hc.out(sh.proof_words());
+  RCHK(hc.rc);
+  RCHK(ronk_fri_prove_dev(h, de, ds, dw, dp, nullptr));
+  return hc.get(proof, dp, sh.proof_words() * 8);
 }
 
 extern "C" int ronk_fri_verify(const ronk_fri* h, const uint64_t* proof, const uint64_t* seed, int* status) {
   if (!h || !proof || !seed || !status) return RONK_ERR_INVALID;
   RCHK(need_device());
   const FriShape& sh = h->sh;
-  DevBuf dp, ds, dst;
-  RCHK(dp.alloc(sh.proof_words() * 8)); RCHK(ds.alloc(sh.d * 8)); RCHK(dst.alloc(8));
-  HIPCHK(hipMemcpy(dp.p, proof, sh.proof_words() * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds.p, seed, sh.d * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_fri_verify_dev(h, dp.u(), ds.u(), (int*)dst.p, nullptr));
-  HIPCHK(hipMemcpy(status, dst.p, sizeof(int), hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64 *dp = hc.in(proof, sh.proof_words()), *ds = hc.in(seed, sh.d);
+  u64* dst = hc.out(1);
+  RCHK(hc.rc);
+  RCHK(ronk_fri_verify_dev(h, dp, ds, (int*)dst, nullptr));
+  return hc.get(status, dst, sizeof(int));
 }

@@ -2,10 +2,11 @@
 // "batched FRI polynomial commitment"; csrc/deep_kernels.h).  The Merkle tree, the openings, the extension
 // FRI prover and verifier are the merged ones, used through their own entry points; this file adds the evaluation of the columns
 // at extension points, the DEEP combination of the matrix, its check in the verifier and the transcript step that binds them.
+// The launch context and the policy dispatch are those of csrc/ext2_launch.h.
 #include "runtime.h"
 #include "hip_launch.h"
 #include "poseidon_handle.h"
-#include "ext2_kernels.h"
+#include "ext2_launch.h"
 #include "deep_kernels.h"
 
 // ------------------------------------------------------------------------------------- handle
@@ -15,9 +16,7 @@ struct ronk_pcs {
   u64 p = 0;
   u32 C = 0, K = 0, log2_blowup = 0;
   FriShape sh;                  // that of the FRI handle
-  bool mont = false, w7 = false;
-  FriConsts k;
-  u64 w_reg = 0;
+  Ext2Launch c;                 // the field policy, its constants, W
   DeepDomain dm{};
   u64* d_dom = nullptr;         // lo, hi of the domain
   u64* d_tab = nullptr;         // the table of the call in flight (deep_tab_words)
@@ -31,33 +30,22 @@ struct ronk_pcs {
   u64 workspace_words() const { return small_words() + 2 * sh.size(0) + sh.workspace_words(); }
 };
 
-// run the statement with FF bound to the field policy
-#define PCS_DISPATCH_F(mont, w7, ...)                          \
-  do {                                                         \
-    if (mont) { typedef FriMont FF; __VA_ARGS__; }             \
-    else if (w7) { typedef FriGlW7 FF; __VA_ARGS__; }          \
-    else { typedef FriGl FF; __VA_ARGS__; }                    \
+// run the statement with KK bound to the number of points ...
+#define PCS_DISPATCH_K(Kv, ...)                             \
+  do {                                                      \
+    switch (Kv) {                                           \
+      case 1: { constexpr int KK = 1; __VA_ARGS__; } break; \
+      case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
+      case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
+      case 4: { constexpr int KK = 4; __VA_ARGS__; } break; \
+      case 5: { constexpr int KK = 5; __VA_ARGS__; } break; \
+      case 6: { constexpr int KK = 6; __VA_ARGS__; } break; \
+      case 7: { constexpr int KK = 7; __VA_ARGS__; } break; \
+      default: { constexpr int KK = 8; __VA_ARGS__; } break; \
+    }                                                       \
   } while (0)
-#define PCS_DISPATCH_K(F, Kv, ...)                                                  \
-  do {                                                                              \
-    switch (Kv) {                                                                   \
-      case 1: { typedef F FF; constexpr int KK = 1; __VA_ARGS__; } break;           \
-      case 2: { typedef F FF; constexpr int KK = 2; __VA_ARGS__; } break;           \
-      case 3: { typedef F FF; constexpr int KK = 3; __VA_ARGS__; } break;           \
-      case 4: { typedef F FF; constexpr int KK = 4; __VA_ARGS__; } break;           \
-      case 5: { typedef F FF; constexpr int KK = 5; __VA_ARGS__; } break;           \
-      case 6: { typedef F FF; constexpr int KK = 6; __VA_ARGS__; } break;           \
-      case 7: { typedef F FF; constexpr int KK = 7; __VA_ARGS__; } break;           \
-      default: { typedef F FF; constexpr int KK = 8; __VA_ARGS__; } break;          \
-    }                                                                               \
-  } while (0)
-// ... and KK to the handle's number of points
-#define PCS_DISPATCH(h, ...)                                               \
-  do {                                                                     \
-    if ((h)->mont) PCS_DISPATCH_K(FriMont, (h)->K, __VA_ARGS__);           \
-    else if ((h)->w7) PCS_DISPATCH_K(FriGlW7, (h)->K, __VA_ARGS__);        \
-    else PCS_DISPATCH_K(FriGl, (h)->K, __VA_ARGS__);                       \
-  } while (0)
+// ... and FF to the handle's field policy
+#define PCS_DISPATCH(h, ...) EXT2_DISPATCH3((h)->c, PCS_DISPATCH_K((h)->K, __VA_ARGS__))
 
 // ------------------------------------------------------------------------------------- kernels
 // One workgroup per column: lane l takes the coefficients l + 256 r, the shares meet in an LDS tree.  y: planar [2][K C].
@@ -233,15 +221,12 @@ extern "C" int ronk_pcs_create(ronk_pcs** out, const ronk_poseidon* pos, uint64_
   ronk_pcs* h = new ronk_pcs;
   pcs_shape(log2_n, log2_arity, log2_final, n_queries, digest_len, n_columns, n_points, h);
   h->pos = pos; h->p = pos->p; h->log2_blowup = log2_blowup;
-  h->mont = h->p != RONK_GOLDILOCKS_P;
-  h->w7 = !h->mont && w % h->p == 7;
-  h->k = ext2_host_consts(h->mont, h->p);
-  h->w_reg = ext2_reg_form(h->mont, h->p, w);
+  h->c = ext2_launch(h->p, w);
   int rc = ronk_fri_create_ext(&h->fri, pos, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, 1);
   if (rc != RONK_OK) { ronk_pcs_destroy(h); return rc; }
   const u32 kb = deep_kbits(log2_n);
   std::vector<u64> dom(((size_t)1 << kb) + ((size_t)1 << (log2_n - kb)));
-  deep_host_domain(h->mont, h->p, g % h->p, coset_shift, log2_n, dom.data(), dom.data() + ((size_t)1 << kb), &h->dm.iota, &h->dm.sinv);
+  deep_host_domain(h->c.mont, h->p, g % h->p, coset_shift, log2_n, dom.data(), dom.data() + ((size_t)1 << kb), &h->dm.iota, &h->dm.sinv);
   rc = upload(dom, &h->d_dom);
   if (rc != RONK_OK) { ronk_pcs_destroy(h); return rc; }
   h->dm.lo = h->d_dom; h->dm.hi = h->d_dom + ((size_t)1 << kb); h->dm.kbits = kb; h->dm.log2n = log2_n;
@@ -253,10 +238,8 @@ extern "C" int ronk_pcs_create(ronk_pcs** out, const ronk_poseidon* pos, uint64_
 }
 
 // ------------------------------------------------------------------------------------- device entry points
-static int eval_batch_launch(bool mont, bool w7, const FriConsts& k, u64 w_reg, const u64* d_coef, u32 C, u64 d, const u64* d_z, u32 K,
-                             u64* d_y, hipStream_t s) {
-  PCS_DISPATCH_F(mont, w7, hipLaunchKernelGGL((deep_eval_kernel<FF>), dim3(C), dim3(DEEP_EVAL_LANES), 0, s, k, w_reg, d_coef, d, d_z, K, C,
-                                             d_y));
+static int eval_batch_launch(const Ext2Launch& c, const u64* d_coef, u32 C, u64 d, const u64* d_z, u32 K, u64* d_y, hipStream_t s) {
+  EXT2_DISPATCH3(c, hipLaunchKernelGGL((deep_eval_kernel<FF>), dim3(C), dim3(DEEP_EVAL_LANES), 0, s, c.k, c.w, d_coef, d, d_z, K, C, d_y));
   HIPCHK(hipGetLastError());
   return RONK_OK;
 }
@@ -267,9 +250,7 @@ extern "C" int ronk_ext2_poly_eval_batch_dev(uint64_t p, uint64_t w, const uint6
   RCHK(ronk_ext2_check(p, w));
   if (n_points > DEEP_MAX_K || n_columns > (1u << 24)) return RONK_ERR_UNSUPPORTED;
   RCHK(need_device());
-  const bool mont = p != RONK_GOLDILOCKS_P;
-  return eval_batch_launch(mont, !mont && w % p == 7, ext2_host_consts(mont, p), ext2_reg_form(mont, p, w), d_coef, n_columns, d, d_z,
-                           n_points, d_y, (hipStream_t)stream);
+  return eval_batch_launch(ext2_launch(p, w), d_coef, n_columns, d, d_z, n_points, d_y, (hipStream_t)stream);
 }
 
 static int pcs_transcript_dev(const ronk_pcs* h, const u64* d_seed, const u64* d_root, const u64* d_z, const u64* d_y, u64* d_a,
@@ -283,7 +264,7 @@ static int pcs_transcript_dev(const ronk_pcs* h, const u64* d_seed, const u64* d
 
 // the table of a call from alpha, the points and the claims; ORs bit 32 into *d_status
 static int pcs_prep_dev(const ronk_pcs* h, const u64* d_alpha, const u64* d_z, const u64* d_y, int* d_status, hipStream_t s) {
-  PCS_DISPATCH_F(h->mont, h->w7, hipLaunchKernelGGL((deep_prep_kernel<FF>), dim3(1), dim3(256), 0, s, h->k, h->w_reg, h->dm, d_alpha, d_z,
+  EXT2_DISPATCH3(h->c, hipLaunchKernelGGL((deep_prep_kernel<FF>), dim3(1), dim3(256), 0, s, h->c.k, h->c.w, h->dm, d_alpha, d_z,
                                                    d_y, h->K, h->C, h->d_tab, d_status));
   HIPCHK(hipGetLastError());
   return RONK_OK;
@@ -291,7 +272,7 @@ static int pcs_prep_dev(const ronk_pcs* h, const u64* d_alpha, const u64* d_z, c
 static int pcs_combine_launch(const ronk_pcs* h, const u64* d_M, u64* d_G, hipStream_t s) {
   const u64 q = h->sh.size(0) >> 2;
   if ((q + 255) / 256 > 0x7fffffffull) return RONK_ERR_UNSUPPORTED;
-  PCS_DISPATCH(h, hipLaunchKernelGGL((deep_combine_kernel<FF, KK>), dim3((u32)((q + 255) / 256)), dim3(256), 0, s, h->k, h->w_reg, h->dm,
+  PCS_DISPATCH(h, hipLaunchKernelGGL((deep_combine_kernel<FF, KK>), dim3((u32)((q + 255) / 256)), dim3(256), 0, s, h->c.k, h->c.w, h->dm,
                                      h->d_tab, h->d_tab + (u64)DEEP_KW * h->K, h->C, d_M, d_G));
   HIPCHK(hipGetLastError());
   return RONK_OK;
@@ -327,11 +308,11 @@ extern "C" int ronk_pcs_open_dev(const ronk_pcs* h, const uint64_t* d_M, const u
   u64* d_fri_proof = d_proof + h->claims();
   u64* d_leaves = d_fri_proof + h->fri_proof();
   u64* d_paths = d_leaves + Q * h->leaf_len();
-  RCHK(eval_batch_launch(h->mont, h->w7, h->k, h->w_reg, d_coef, h->C, N >> h->log2_blowup, d_z, h->K, d_claims, s));
+  RCHK(eval_batch_launch(h->c, d_coef, h->C, N >> h->log2_blowup, d_z, h->K, d_claims, s));
   RCHK(pcs_transcript_dev(h, d_seed, d_tree + ronk_merkle_tree_words(m, D) - D, d_z, d_claims, d_a, s));
   RCHK(ronk_deep_combine_dev(h, d_M, d_claims, d_z, d_a, d_G, d_status, stream));
   RCHK(ronk_fri_prove_dev(h->fri, d_G, d_a, d_fri_work, d_fri_proof, stream));
-  PCS_DISPATCH_F(h->mont, h->w7, hipLaunchKernelGGL((pcs_gather_kernel<FF>), dim3(grid_for(Q * h->leaf_len())), dim3(256), 0, s, h->k, d_M,
+  EXT2_DISPATCH3(h->c, hipLaunchKernelGGL((pcs_gather_kernel<FF>), dim3(grid_for(Q * h->leaf_len())), dim3(256), 0, s, h->c.k, d_M,
                                                    sh.log2m(0), h->leaf_len(), d_idx, Q, d_leaves));
   HIPCHK(hipGetLastError());
   return ronk_merkle_open_dev(d_tree, m, D, d_idx, Q, d_paths, d_st, stream);
@@ -354,7 +335,7 @@ extern "C" int ronk_pcs_verify_dev(const ronk_pcs* h, const uint64_t* d_root, co
   RCHK(ronk_fri_verify_dev(h->fri, d_fri_proof, d_a, d_status, stream));   // writes the status: bits 1 / 2 / 4
   RCHK(pcs_prep_dev(h, d_a, d_z, d_claims, d_status, s));
   RCHK(ronk_merkle_verify_dev(h->pos, d_leaves, Q, h->leaf_len(), h->leaf_len(), 1, d_idx, d_paths, m, D, d_root, d_ok, stream));
-  PCS_DISPATCH(h, hipLaunchKernelGGL((deep_check_kernel<FF, KK>), dim3(grid_for(Q << sh.eta)), dim3(256), 0, s, h->k, h->w_reg, h->dm,
+  PCS_DISPATCH(h, hipLaunchKernelGGL((deep_check_kernel<FF, KK>), dim3(grid_for(Q << sh.eta)), dim3(256), 0, s, h->c.k, h->c.w, h->dm,
                                      h->d_tab, h->d_tab + (u64)DEEP_KW * h->K, h->C, sh.eta, Q, d_idx, d_leaves,
                                      d_fri_proof + sh.leaf_off(0), d_ok, d_status));
   HIPCHK(hipGetLastError());
@@ -368,25 +349,24 @@ extern "C" int ronk_ext2_poly_eval_batch(uint64_t p, uint64_t w, const uint64_t*
   RCHK(ronk_ext2_check(p, w));
   if (n_points > DEEP_MAX_K || n_columns > (1u << 24)) return RONK_ERR_UNSUPPORTED;
   RCHK(need_device());
-  const size_t nc = (size_t)n_columns * d, ny = 2 * (size_t)n_points * n_columns;
-  DevBuf dc, dz, dy;
-  RCHK(dc.alloc(nc * 8)); RCHK(dz.alloc(2 * (size_t)n_points * 8)); RCHK(dy.alloc(ny * 8));
-  HIPCHK(hipMemcpy(dc.p, coef, nc * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dz.p, z, 2 * (size_t)n_points * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_ext2_poly_eval_batch_dev(p, w, dc.u(), n_columns, d, dz.u(), n_points, dy.u(), nullptr));
-  HIPCHK(hipMemcpy(y, dy.p, ny * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  const size_t ny = 2 * (size_t)n_points * n_columns;
+  HostCall hc;
+  const u64 *dc = hc.in(coef, (size_t)n_columns * d), *dz = hc.in(z, 2 * (size_t)n_points);
+  u64* dy = hc.out(ny);
+  RCHK(hc.rc);
+  RCHK(ronk_ext2_poly_eval_batch_dev(p, w, dc, n_columns, d, dz, n_points, dy, nullptr));
+  return hc.get(y, dy, ny * 8);
 }
 
 extern "C" int ronk_pcs_commit(const ronk_pcs* h, const uint64_t* M, uint64_t* tree) {
   if (!h || !M || !tree) return RONK_ERR_INVALID;
-  const size_t nm = (size_t)h->C * h->sh.size(0), nt = ronk_merkle_tree_words((size_t)1 << h->sh.log2m(0), h->sh.d);
-  DevBuf dm, dt;
-  RCHK(dm.alloc(nm * 8)); RCHK(dt.alloc(nt * 8));
-  HIPCHK(hipMemcpy(dm.p, M, nm * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_pcs_commit_dev(h, dm.u(), dt.u(), nullptr));
-  HIPCHK(hipMemcpy(tree, dt.p, nt * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  const size_t nt = ronk_merkle_tree_words((size_t)1 << h->sh.log2m(0), h->sh.d);
+  HostCall hc;
+  const u64* dm = hc.in(M, (size_t)h->C * h->sh.size(0));
+  u64* dt = hc.out(nt);
+  RCHK(hc.rc);
+  RCHK(ronk_pcs_commit_dev(h, dm, dt, nullptr));
+  return hc.get(tree, dt, nt * 8);
 }
 
 extern "C" int ronk_pcs_open(const ronk_pcs* h, const uint64_t* M, const uint64_t* tree, const uint64_t* coef, const uint64_t* z,
@@ -395,32 +375,23 @@ extern "C" int ronk_pcs_open(const ronk_pcs* h, const uint64_t* M, const uint64_
   const FriShape& sh = h->sh;
   const size_t nm = (size_t)h->C * sh.size(0), nt = ronk_merkle_tree_words((size_t)1 << sh.log2m(0), sh.d);
   const size_t nc = (size_t)h->C * (sh.size(0) >> h->log2_blowup);
-  DevBuf dm, dt, dc, dz, ds, dw, dp, dst;
-  RCHK(dm.alloc(nm * 8)); RCHK(dt.alloc(nt * 8)); RCHK(dc.alloc(nc * 8)); RCHK(dz.alloc(2 * (size_t)h->K * 8)); RCHK(ds.alloc(sh.d * 8));
-  RCHK(dw.alloc(h->workspace_words() * 8)); RCHK(dp.alloc(h->proof_words() * 8)); RCHK(dst.alloc(8));
-  HIPCHK(hipMemcpy(dm.p, M, nm * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dt.p, tree, nt * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dc.p, coef, nc * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dz.p, z, 2 * (size_t)h->K * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds.p, seed, sh.d * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_pcs_open_dev(h, dm.u(), dt.u(), dc.u(), dz.u(), ds.u(), dw.u(), dp.u(), (int*)dst.p, nullptr));
-  HIPCHK(hipMemcpy(proof, dp.p, h->proof_words() * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(status, dst.p, sizeof(int), hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64 *dm = hc.in(M, nm), *dt = hc.in(tree, nt), *dc = hc.in(coef, nc), *dz = hc.in(z, 2 * (size_t)h->K), *ds = hc.in(seed, sh.d);
+  u64 *dw = hc.out(h->workspace_words()), *dp = hc.out(h->proof_words()), *dst = hc.out(1);
+  RCHK(hc.rc);
+  RCHK(ronk_pcs_open_dev(h, dm, dt, dc, dz, ds, dw, dp, (int*)dst, nullptr));
+  RCHK(hc.get(proof, dp, h->proof_words() * 8));
+  return hc.get(status, dst, sizeof(int));
 }
 
 extern "C" int ronk_pcs_verify(const ronk_pcs* h, const uint64_t* root, const uint64_t* z, const uint64_t* seed, const uint64_t* proof,
                                int* status) {
   if (!h || !root || !z || !seed || !proof || !status) return RONK_ERR_INVALID;
   const FriShape& sh = h->sh;
-  DevBuf dr, dz, ds, dp, dst;
-  RCHK(dr.alloc(sh.d * 8)); RCHK(dz.alloc(2 * (size_t)h->K * 8)); RCHK(ds.alloc(sh.d * 8)); RCHK(dp.alloc(h->proof_words() * 8));
-  RCHK(dst.alloc(8));
-  HIPCHK(hipMemcpy(dr.p, root, sh.d * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dz.p, z, 2 * (size_t)h->K * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds.p, seed, sh.d * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dp.p, proof, h->proof_words() * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_pcs_verify_dev(h, dr.u(), dz.u(), ds.u(), dp.u(), (int*)dst.p, nullptr));
-  HIPCHK(hipMemcpy(status, dst.p, sizeof(int), hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64 *dr = hc.in(root, sh.d), *dz = hc.in(z, 2 * (size_t)h->K), *ds = hc.in(seed, sh.d), *dp = hc.in(proof, h->proof_words());
+  u64* dst = hc.out(1);
+  RCHK(hc.rc);
+  RCHK(ronk_pcs_verify_dev(h, dr, dz, ds, dp, (int*)dst, nullptr));
+  return hc.get(status, dst, sizeof(int));
 }

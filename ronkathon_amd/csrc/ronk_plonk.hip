@@ -1,17 +1,15 @@
 // ronk_plonk.hip -- C ABI of libronk_ntt.so, part 13: the fused PLONK quotient on the evaluation coset (csrc/plonk_kernels.h;
-// include/ronk_ntt.h "PLONK quotient").  One launch per call, no host round trip and no library workspace:
-// the _dev call is legal under stream capture.
+// csrc/ext2_launch.h; include/ronk_ntt.h "PLONK quotient").  One launch per call, no host round trip and no
+// library workspace: the _dev call is legal under stream capture.
 #include "runtime.h"
 #include "hip_launch.h"
-#include "ext2_kernels.h"
+#include "ext2_launch.h"
 #include "plonk_kernels.h"
 
 struct ronk_plonk {
   u64 p = 0;
   u32 log2m = 0;
-  bool mont = false, w7 = false;
-  FriConsts k;
-  u64 w_reg = 0;
+  Ext2Launch c;            // the field policy, its constants, W
   DeepDomain dm{};
   PlonkTab tab{};
   u64* d_dom = nullptr;    // lo, hi of the domain
@@ -46,22 +44,20 @@ extern "C" int ronk_plonk_create(ronk_plonk** out, uint64_t p, uint64_t g, uint6
   RCHK(need_device());
   ronk_plonk* h = new ronk_plonk;
   h->p = p; h->log2m = log2_n + log2_blowup;
-  h->mont = p != RONK_GOLDILOCKS_P;
-  h->w7 = !h->mont && w % p == 7;
-  h->k = ext2_host_consts(h->mont, p);
-  h->w_reg = ext2_reg_form(h->mont, p, w);
+  h->c = ext2_launch(p, w);
+  const bool mont = h->c.mont;
   const u32 kb = deep_kbits(h->log2m);
   std::vector<u64> dom(((size_t)1 << kb) + ((size_t)1 << (h->log2m - kb))), vinv((size_t)1 << log2_blowup);
-  deep_host_domain(h->mont, p, g % p, coset_shift, h->log2m, dom.data(), dom.data() + ((size_t)1 << kb), &h->dm.iota, &h->dm.sinv);
-  plonk_host_vanishing(h->mont, p, g % p, coset_shift, log2_n, log2_blowup, vinv.data());
+  deep_host_domain(mont, p, g % p, coset_shift, h->log2m, dom.data(), dom.data() + ((size_t)1 << kb), &h->dm.iota, &h->dm.sinv);
+  plonk_host_vanishing(mont, p, g % p, coset_shift, log2_n, log2_blowup, vinv.data());
   int rc = upload(dom, &h->d_dom);
   if (rc == RONK_OK) rc = upload(vinv, &h->d_vinv);
   if (rc != RONK_OK) { ronk_plonk_destroy(h); return rc; }
   h->dm.lo = h->d_dom; h->dm.hi = h->d_dom + ((size_t)1 << kb); h->dm.kbits = kb; h->dm.log2n = h->log2m;
   h->tab.vinv = h->d_vinv; h->tab.log2b = log2_blowup;
-  h->tab.ninv = ext2_reg_form(h->mont, p, h_powmod(((u64)1 << log2_n) % p, p - 2, p));
-  h->tab.rho = ext2_reg_form(h->mont, p, h->log2m >= 3 ? h_powmod(g, (p - 1) >> 3, p) : 1);
-  for (int c = 0; c < 3; c++) h->tab.k[c] = ext2_reg_form(h->mont, p, k[c]);
+  h->tab.ninv = ext2_reg_form(mont, p, h_powmod(((u64)1 << log2_n) % p, p - 2, p));
+  h->tab.rho = ext2_reg_form(mont, p, h->log2m >= 3 ? h_powmod(g, (p - 1) >> 3, p) : 1);
+  for (int c = 0; c < 3; c++) h->tab.k[c] = ext2_reg_form(mont, p, k[c]);
   *out = h;
   return RONK_OK;
 }
@@ -72,11 +68,11 @@ static void plonk_launch(const ronk_plonk* h, const PlonkCols& cols, u64* d_T, h
   constexpr u32 LP = PlonkRows<FF>::LOG2;
   const u64 M = (u64)1 << h->log2m;
   if (h->log2m < LP)
-    hipLaunchKernelGGL((plonk_quotient_kernel<FF, 1>), dim3((u32)((M + PLONK_LANES - 1) / PLONK_LANES)), dim3(PLONK_LANES), 0, s, h->k,
-                       h->w_reg, h->dm, h->tab, cols, d_T);
+    hipLaunchKernelGGL((plonk_quotient_kernel<FF, 1>), dim3((u32)((M + PLONK_LANES - 1) / PLONK_LANES)), dim3(PLONK_LANES), 0, s, h->c.k,
+                       h->c.w, h->dm, h->tab, cols, d_T);
   else
     hipLaunchKernelGGL((plonk_quotient_kernel<FF, 1 << LP>), dim3((u32)(((M >> LP) + PLONK_LANES - 1) / PLONK_LANES)), dim3(PLONK_LANES),
-                       0, s, h->k, h->w_reg, h->dm, h->tab, cols, d_T);
+                       0, s, h->c.k, h->c.w, h->dm, h->tab, cols, d_T);
 }
 
 extern "C" int ronk_plonk_quotient_dev(const ronk_plonk* h, const uint64_t* d_wires, const uint64_t* d_sel, const uint64_t* d_sigma,
@@ -84,9 +80,7 @@ extern "C" int ronk_plonk_quotient_dev(const ronk_plonk* h, const uint64_t* d_wi
                                        const uint64_t* d_gamma, uint64_t* d_T, void* stream) {
   if (!h || !d_wires || !d_sel || !d_sigma || !d_Z || !d_alpha || !d_beta || !d_gamma || !d_T) return RONK_ERR_INVALID;
   const PlonkCols cols{d_wires, d_sel, d_sigma, d_pi, d_Z, d_alpha, d_beta, d_gamma};
-  if (h->mont) plonk_launch<FriMont>(h, cols, d_T, (hipStream_t)stream);
-  else if (h->w7) plonk_launch<FriGlW7>(h, cols, d_T, (hipStream_t)stream);
-  else plonk_launch<FriGl>(h, cols, d_T, (hipStream_t)stream);
+  EXT2_DISPATCH3(h->c, plonk_launch<FF>(h, cols, d_T, (hipStream_t)stream));
   HIPCHK(hipGetLastError());
   return RONK_OK;
 }
@@ -96,17 +90,11 @@ extern "C" int ronk_plonk_quotient(const ronk_plonk* h, const uint64_t* wires, c
                                    const uint64_t* gamma, uint64_t* T) {
   if (!h || !wires || !sel || !sigma || !Z || !alpha || !beta || !gamma || !T) return RONK_ERR_INVALID;
   const size_t M = (size_t)1 << h->log2m;
-  const struct { const u64* src; size_t words; } in[8] = {{wires, 3 * M}, {sel, 5 * M}, {sigma, 3 * M}, {pi, M},
-                                                          {Z, 2 * M},     {alpha, 2},   {beta, 2},      {gamma, 2}};
-  DevBuf d[8], out;
-  for (int j = 0; j < 8; j++) {
-    if (!in[j].src) continue;
-    RCHK(d[j].alloc(in[j].words * 8));
-    HIPCHK(hipMemcpy(d[j].p, in[j].src, in[j].words * 8, hipMemcpyHostToDevice));
-  }
-  RCHK(out.alloc(2 * M * 8));
-  RCHK(ronk_plonk_quotient_dev(h, d[0].u(), d[1].u(), d[2].u(), pi ? d[3].u() : nullptr, d[4].u(), d[5].u(), d[6].u(), d[7].u(), out.u(),
-                               nullptr));
-  HIPCHK(hipMemcpy(T, out.p, 2 * M * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64 *dw = hc.in(wires, 3 * M), *dsel = hc.in(sel, 5 * M), *dsg = hc.in(sigma, 3 * M), *dpi = hc.in(pi, M);   // pi is optional
+  const u64 *dZ = hc.in(Z, 2 * M), *da = hc.in(alpha, 2), *db = hc.in(beta, 2), *dg = hc.in(gamma, 2);
+  u64* dT = hc.out(2 * M);
+  RCHK(hc.rc);
+  RCHK(ronk_plonk_quotient_dev(h, dw, dsel, dsg, dpi, dZ, da, db, dg, dT, nullptr));
+  return hc.get(T, dT, 2 * M * 8);
 }

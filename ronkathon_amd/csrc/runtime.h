@@ -5,12 +5,15 @@
 //   ronk_callers.hip  evaluate, division, Lagrange evaluate, Reed-Solomon encode/decode, KZG commit (MSM)
 //   ronk_dist.hip     multi-GPU four-step phases
 //   ronk_recover.hip  the product tree and erasure recovery;  ronk_multipoint.hip  multipoint evaluation / interpolation on it
+//   ronk_ext2.hip, ronk_accum.hip, ronk_plonk.hip, ronk_pcs.hip, ronk_fri.hip  the extension-field family: one launch context and
+//                     dispatch (ext2_launch.h), host-pointer forms on HostCall (below)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <deque>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -102,6 +105,31 @@ struct DevBuf {
     return RONK_OK;
   }
   u64* u() const { return (u64*)p; }
+};
+
+// The device side of a host-pointer entry point: the buffers live as long as the object.  A failed step is kept in `rc` and
+// every later in / out is skipped, so a caller tests rc once, before its _dev call on the null stream, and ends with get.
+struct HostCall {
+  std::deque<DevBuf> bufs;
+  int rc = RONK_OK;
+  u64* out(size_t words) {   // an output or a workspace
+    if (rc != RONK_OK) return nullptr;
+    bufs.emplace_back();
+    rc = bufs.back().alloc(words * 8);
+    return bufs.back().u();
+  }
+  u64* in(const u64* h, size_t words) {   // the device copy of h[words]; an optional input that is NULL stays nullptr
+    u64* d = h ? out(words) : nullptr;
+    if (d && rc == RONK_OK && words) {
+      hipError_t e = hipMemcpy(d, h, words * 8, hipMemcpyHostToDevice);
+      if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy (host to device)");
+    }
+    return d;
+  }
+  int get(void* h, const void* d, size_t bytes) const {
+    HIPCHK(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
+    return RONK_OK;
+  }
 };
 
 static inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }

@@ -14,44 +14,7 @@
 
 #include "../../ronkathon_amd/csrc/accum_kernels.h"
 using namespace ronk;
-typedef unsigned __int128 u128;
-
-static u64 g_rng;
-static u64 rnd() {   // SplitMix64
-  u64 z = (g_rng += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-static int g_fail = 0;
-#define CHECK(c, ...) do { if (!(c)) { if (g_fail++ < 10) { printf("FAIL %s:%d ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
-
-// ---------------------------------------------------------------------------------------------------- the restatement
-static u64 r_mul(u64 a, u64 b, u64 p) { return (u64)(((u128)a * b) % p); }
-static u64 r_add(u64 a, u64 b, u64 p) { const u128 s = (u128)a + b; return (u64)(s >= p ? s - p : s); }   // a, b < p
-static u64 r_sub(u64 a, u64 b, u64 p) { return a >= b ? a - b : a + (p - b); }
-static u64 r_pow(u64 a, u64 e, u64 p) {
-  u64 r = 1 % p;
-  while (e) { if (e & 1) r = r_mul(r, a, p); a = r_mul(a, a, p); e >>= 1; }
-  return r;
-}
-static u64 edge_word(u64 p) {
-  const u64 c = rnd() % 8;
-  return c == 0 ? p - 1 : c == 1 ? 0 : c == 2 ? p + rnd() % 5 : rnd();
-}
-struct R2 { u64 c0, c1; };
-static bool operator==(R2 a, R2 b) { return a.c0 == b.c0 && a.c1 == b.c1; }
-static R2 x_add(R2 a, R2 b, u64 p) { return R2{r_add(a.c0, b.c0, p), r_add(a.c1, b.c1, p)}; }
-static R2 x_scale(R2 a, u64 s, u64 p) { return R2{r_mul(a.c0, s, p), r_mul(a.c1, s, p)}; }
-static R2 x_mul(R2 a, R2 b, u64 w, u64 p) {
-  return R2{r_add(r_mul(a.c0, b.c0, p), r_mul(w, r_mul(a.c1, b.c1, p), p), p), r_add(r_mul(a.c0, b.c1, p), r_mul(a.c1, b.c0, p), p)};
-}
-// (a0, -a1) / norm; zero for the zero element
-static R2 x_inv(R2 a, u64 w, u64 p) {
-  const u64 n = r_sub(r_mul(a.c0, a.c0, p), r_mul(w, r_mul(a.c1, a.c1, p), p), p);
-  return x_scale(R2{a.c0, r_sub(0, a.c1, p)}, r_pow(n, p - 2, p), p);
-}
-static R2 red(R2 a, u64 p) { return R2{a.c0 % p, a.c1 % p}; }
+#include "emu_ref.h"
 
 // ---------------------------------------------------------------------------------------------------- the kernels, lane by lane
 template <class O>

@@ -1,7 +1,7 @@
 // emu_deep.cpp -- the bodies of csrc/deep_kernels.h (the table of a call, the DEEP combination of a lane's points for the combine
 // kernel's four points and the check kernel's one, the evaluation at extension points) compiled for the host and compared with a
-// plain `unsigned __int128 % p` restatement in this file: the double sum of the definition and Horner's rule.  The base-field
-// helpers are those of emu_fri.cpp.  Test infrastructure only; never part of the product library.
+// plain `unsigned __int128 % p` restatement in this file: the double sum of the definition and Horner's rule, over the arithmetic
+// of emu_ref.h (which emu_fri.cpp brings in).  Test infrastructure only; never part of the product library.
 //
 //   emu_deep <p> <g> [w]   last line "OK ..." on success; w defaults to g.  Goldilocks runs the Goldilocks policy, its W = 7 form
 //                          when w = 7, AND the Montgomery policy.
@@ -13,21 +13,6 @@
 #include "../../ronkathon_amd/csrc/deep_kernels.h"
 
 // ---------------------------------------------------------------------------------------------------- the restatement
-struct R2 { u64 c0, c1; };
-static bool operator==(R2 a, R2 b) { return a.c0 == b.c0 && a.c1 == b.c1; }
-static R2 x_add(R2 a, R2 b, u64 p) { return R2{r_add(a.c0, b.c0, p), r_add(a.c1, b.c1, p)}; }
-static R2 x_sub(R2 a, R2 b, u64 p) { return R2{r_sub(a.c0, b.c0, p), r_sub(a.c1, b.c1, p)}; }
-static R2 x_scale(R2 a, u64 s, u64 p) { return R2{r_mul(a.c0, s, p), r_mul(a.c1, s, p)}; }
-static R2 x_mul(R2 a, R2 b, u64 w, u64 p) {
-  return R2{r_add(r_mul(a.c0, b.c0, p), r_mul(w, r_mul(a.c1, b.c1, p), p), p), r_add(r_mul(a.c0, b.c1, p), r_mul(a.c1, b.c0, p), p)};
-}
-// (a0, -a1) / norm; zero for the zero element
-static R2 x_inv(R2 a, u64 w, u64 p) {
-  const u64 n = r_sub(r_mul(a.c0, a.c0, p), r_mul(w, r_mul(a.c1, a.c1, p), p), p);
-  return x_scale(R2{a.c0, r_sub(0, a.c1, p)}, r_pow(n, p - 2, p), p);
-}
-static R2 red(R2 a, u64 p) { return R2{a.c0 % p, a.c1 % p}; }
-
 // G at the point x from the column values there: sum_k sum_c alpha^(k C + c) (col[c] - y[k][c]) / (x - z_k), term by term
 static R2 ref_point(u64 p, u64 w, const std::vector<u64>& col, u64 x, const std::vector<R2>& ys, const std::vector<R2>& zs, R2 alpha) {
   const size_t C = col.size(), K = zs.size();

@@ -1,7 +1,7 @@
 // emu_ext2.cpp -- the quadratic extension of csrc/ext2.h and the extension FRI bodies of csrc/fri_kernels.h (fold, transcript,
 // query check, final-degree sums) compiled for the host and compared with a plain `unsigned __int128 % p` restatement in this
-// file.  The base-field helpers, tables and Poseidon setup are those of emu_fri.cpp.  W is the field's generator g.  Test
-// infrastructure only; never part of the product library.
+// file.  The tables and Poseidon setup are those of emu_fri.cpp, the arithmetic of the restatement that of emu_ref.h.  W is the
+// field's generator g.  Test infrastructure only; never part of the product library.
 //
 //   emu_ext2 <p> <g>     last line "OK ..." on success.  Goldilocks with g = 7 runs the shift policy, its W = 7 form (shift_policy=2)
 //                        AND the Montgomery policy.
@@ -10,15 +10,6 @@
 #undef main
 
 // ---------------------------------------------------------------------------------------------------- the restatement
-struct R2 { u64 c0, c1; };
-static bool operator==(R2 a, R2 b) { return a.c0 == b.c0 && a.c1 == b.c1; }
-static R2 x_add(R2 a, R2 b, u64 p) { return R2{r_add(a.c0, b.c0, p), r_add(a.c1, b.c1, p)}; }
-static R2 x_sub(R2 a, R2 b, u64 p) { return R2{r_sub(a.c0, b.c0, p), r_sub(a.c1, b.c1, p)}; }
-static R2 x_scale(R2 a, u64 s, u64 p) { return R2{r_mul(a.c0, s, p), r_mul(a.c1, s, p)}; }
-// schoolbook, reduced modulo t^2 - w
-static R2 x_mul(R2 a, R2 b, u64 w, u64 p) {
-  return R2{r_add(r_mul(a.c0, b.c0, p), r_mul(w, r_mul(a.c1, b.c1, p), p), p), r_add(r_mul(a.c0, b.c1, p), r_mul(a.c1, b.c0, p), p)};
-}
 static R2 x_pow(R2 a, u64 e, u64 w, u64 p) {   // multiply e's bits from the top: another order than the body's
   R2 r{1 % p, 0};
   for (int b = 63; b >= 0; b--) {
@@ -27,12 +18,6 @@ static R2 x_pow(R2 a, u64 e, u64 w, u64 p) {   // multiply e's bits from the top
   }
   return r;
 }
-static R2 x_inv(R2 a, u64 w, u64 p) {
-  const u64 n = r_sub(r_mul(a.c0, a.c0, p), r_mul(w, r_mul(a.c1, a.c1, p), p), p);
-  return x_scale(R2{a.c0, r_sub(0, a.c1, p)}, r_pow(n, p - 2, p), p);
-}
-static R2 red(R2 a, u64 p) { return R2{a.c0 % p, a.c1 % p}; }
-
 static std::vector<R2> x_fold2(u64 p, u64 w, const std::vector<R2>& f, R2 beta, u64 s, u64 wn) {
   const size_t h = f.size() / 2;
   const u64 inv2 = r_pow(2, p - 2, p);

@@ -9,21 +9,6 @@
 #include "../../ronkathon_amd/csrc/fri_kernels.h"
 using namespace ronk;
 
-static u64 g_rng;
-static u64 rnd() {   // SplitMix64
-  u64 z = (g_rng += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-static int g_fail = 0;
-#define CHECK(c, ...) do { if (!(c)) { if (g_fail++ < 10) { printf("FAIL %s:%d ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
-
-static u64 r_sub(u64 a, u64 b, u64 p) { return a >= b ? a - b : a + (p - b); }   // a, b < p
-static u64 edge_word(u64 p) {
-  const u64 c = rnd() % 8;
-  return c == 0 ? p - 1 : c == 1 ? 0 : c == 2 ? p + rnd() % 5 : rnd();
-}
 
 // ---------------------------------------------------------------------------------------------------- the restatement
 // f'[i] = (a + b) / 2 + beta (a - b) / (2 x_i), x_i = s w^i

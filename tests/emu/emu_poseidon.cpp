@@ -13,9 +13,8 @@
 
 #include <vector>
 
-typedef uint64_t u64;
+#include "emu_ref.h"
 typedef uint32_t u32;
-typedef unsigned __int128 u128;
 
 // ---------------------------------------------------------------------------------------------------- the restatement
 struct RefParams {
@@ -25,13 +24,6 @@ struct RefParams {
   const u64* rc;    // canonical
   const u64* mds;   // canonical, row-major
 };
-static u64 r_mul(u64 a, u64 b, u64 p) { return (u64)(((u128)a * b) % p); }
-static u64 r_add(u64 a, u64 b, u64 p) { const u128 s = (u128)a + b; return (u64)(s >= p ? s - p : s); }   // a, b < p
-static u64 r_pow(u64 a, u64 e, u64 p) {
-  u64 r = 1 % p;
-  while (e) { if (e & 1) r = r_mul(r, a, p); a = r_mul(a, a, p); e >>= 1; }
-  return r;
-}
 static void ref_permute(const RefParams& P, u64* st) {
   const u32 w = P.width;
   u64 t[16];
@@ -115,16 +107,7 @@ void posref_merkle(u64 p, u32 width, u64 alpha, u32 num_p, u32 num_f, u32 rate, 
 #include "../../ronkathon_amd/csrc/poseidon_kernels.h"
 using namespace ronk;
 
-static u64 g_rng;
-static u64 rnd() {   // SplitMix64
-  u64 z = (g_rng += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-static int g_fail = 0;
 static bool g_negatives = true;   // off for the all-equal matrix: its hash only sees the SUM of what it absorbs
-#define CHECK(c, ...) do { if (!(c)) { if (g_fail++ < 10) { printf("FAIL %s:%d ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
 struct Setup {
   RefParams P;

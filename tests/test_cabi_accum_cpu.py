@@ -73,6 +73,15 @@ def test_scan_argument_errors(L):
         assert dev(2, 1, d, d, 4, 0, None, d, None) == L.ERR_UNSUPPORTED and dev(91, 3, d, d, 4, 0, None, d, None) == L.ERR_NOT_PRIME
         assert hst(GL, 7, None, d, 4, 0, None) == L.ERR_INVALID and hst(GL, 7, d, d, 4, 2, None) == L.ERR_INVALID
         assert hst(GL, 7, d, d, BIG, 0, None) == L.ERR_UNSUPPORTED and hst(GL, 49, d, d, 4, 0, None) == L.ERR_INVALID
+    # the host forms report the arguments' codes before the field's, the _dev forms likewise
+    for name in BASE:
+        hst = getattr(L.lib, name)
+        assert hst(91, None, d, 4, 0, None) == L.ERR_INVALID and hst(91, d, d, 4, 2, None) == L.ERR_INVALID
+        assert hst(91, d, d, BIG, 0, None) == L.ERR_UNSUPPORTED and hst(2, d, d, 4, 0, None) == L.ERR_UNSUPPORTED
+    for name in EXT:
+        hst = getattr(L.lib, name)
+        assert hst(91, 3, d, None, 4, 0, None) == L.ERR_INVALID and hst(91, 3, d, d, 0, 0, None) == L.ERR_INVALID
+        assert hst(91, 3, d, d, BIG, 0, None) == L.ERR_UNSUPPORTED and hst(91, 3, d, d, 4, 0, None) == L.ERR_NOT_PRIME
 
 
 def test_accumulator_argument_errors(L):
@@ -102,6 +111,11 @@ def test_accumulator_argument_errors(L):
     assert L.lib.ronk_logup_sum(GL, 7, None, None, 2, 8, d, d, d, C.byref(st)) == L.ERR_INVALID
     assert L.lib.ronk_logup_sum(GL, 7, d, None, 2, BIG, d, d, d, C.byref(st)) == L.ERR_UNSUPPORTED
     assert L.lib.ronk_logup_sum(GL, 49, d, None, 2, 8, d, d, d, C.byref(st)) == L.ERR_INVALID
+    # a missing pointer before the field, the field before the shape (the order of ronk_accum_check)
+    assert L.lib.ronk_perm_product(91, 3, d, d, d, 3, 8, d, d, d, d, None) == L.ERR_INVALID
+    assert L.lib.ronk_perm_product(91, 3, d, d, d, 17, 8, d, d, d, d, C.byref(st)) == L.ERR_NOT_PRIME
+    assert L.lib.ronk_logup_sum(91, 3, d, None, 2, 8, None, d, d, C.byref(st)) == L.ERR_INVALID
+    assert L.lib.ronk_logup_sum(91, 3, d, None, 2, BIG, d, d, d, C.byref(st)) == L.ERR_NOT_PRIME
     assert st.value == 7
 
 

@@ -72,6 +72,19 @@ def test_null_arguments(L):
     assert L.lib.ronk_ext2_vec_inv_dev(GL, 7, None, d, 4, None, None) == L.ERR_INVALID
 
 
+def test_host_form_precedence(L):
+    """a missing pointer is reported before the field, the field before the device; every host form goes through one helper"""
+    d = C.c_void_p(16)   # never dereferenced: refused first
+    for name in VEC3:
+        f = getattr(L.lib, name)
+        assert f(91, 3, d, None, d, 4) == L.ERR_INVALID and f(91, 3, d, d, None, 4) == L.ERR_INVALID     # the second operand, out
+        assert f(91, 3, d, d, d, 4) == L.ERR_NOT_PRIME and f(2, 1, d, d, d, 4) == L.ERR_UNSUPPORTED
+    for f, extra in ((L.lib.ronk_ext2_vec_neg, ()), (L.lib.ronk_ext2_vec_pow, (5,)), (L.lib.ronk_ext2_vec_inv, ())):
+        assert f(91, 3, None, *extra, d, 4) == L.ERR_INVALID and f(91, 3, d, *extra, None, 4) == L.ERR_INVALID
+        assert f(91, 3, d, *extra, d, 4) == L.ERR_NOT_PRIME and f(2, 1, d, *extra, d, 4) == L.ERR_UNSUPPORTED
+        assert f(GL, 49, d, *extra, d, 4) == L.ERR_INVALID                                                # w a residue
+
+
 @pytest.mark.parametrize("input_ext", [0, 1])
 @pytest.mark.parametrize("shape", [(6, 1, 2, 8, 2), (9, 3, 3, 8, 2), (12, 2, 4, 5, 3), (12, 3, 3, 64, 4), (24, 3, 3, 64, 4), (3, 3, 0, 1, 2),
                                    (20, 2, 8, 100, 8)])

@@ -61,6 +61,10 @@ def test_null_arguments(L):
     st = C.c_int(5)
     assert L.lib.ronk_fri_prove(None, d, d, d) == L.ERR_INVALID
     assert L.lib.ronk_fri_verify(None, d, d, C.byref(st)) == L.ERR_INVALID
+    # every other pointer of the host forms is required too, and is tested before the handle is read
+    assert L.lib.ronk_fri_prove(d, None, d, d) == L.ERR_INVALID and L.lib.ronk_fri_prove(d, d, d, None) == L.ERR_INVALID
+    assert L.lib.ronk_fri_verify(d, d, None, C.byref(st)) == L.ERR_INVALID and L.lib.ronk_fri_verify(d, d, d, None) == L.ERR_INVALID
+    assert st.value == 5
 
 
 @pytest.mark.parametrize("shape", [(6, 1, 2, 8, 2), (9, 3, 3, 8, 2), (12, 2, 4, 5, 3), (12, 3, 3, 64, 4), (24, 3, 3, 64, 4), (3, 3, 0, 1, 1),

@@ -68,6 +68,11 @@ def test_eval_batch_argument_codes(L):
     assert f(GL, 7, d, 1, 1, d, 9, d, None) == L.ERR_UNSUPPORTED         # more than 8 points
     assert L.lib.ronk_ext2_poly_eval_batch(GL, 7, d, 1, 1, d, 9, d) == L.ERR_UNSUPPORTED
     assert L.lib.ronk_ext2_poly_eval_batch(GL, 7, d, 1, 1, None, 1, d) == L.ERR_INVALID
+    # the host form in the order of the _dev form: pointers and counts, the field, the limits
+    assert L.lib.ronk_ext2_poly_eval_batch(GL - 2, 7, d, 0, 1, d, 1, d) == L.ERR_INVALID
+    assert L.lib.ronk_ext2_poly_eval_batch(GL - 2, 7, d, 1, 1, d, 9, d) == L.ERR_NOT_PRIME
+    assert L.lib.ronk_ext2_poly_eval_batch(GL, 49, d, 1, 1, d, 1, d) == L.ERR_INVALID
+    assert f(GL - 2, 7, d, 0, 1, d, 1, d, None) == L.ERR_INVALID and f(GL - 2, 7, d, 1, 1, d, 9, d, None) == L.ERR_NOT_PRIME
 
 
 def test_null_arguments(L):
@@ -85,6 +90,12 @@ def test_null_arguments(L):
     assert L.lib.ronk_pcs_commit(None, d, d) == L.ERR_INVALID
     assert L.lib.ronk_pcs_open(None, d, d, d, d, d, d, C.byref(st)) == L.ERR_INVALID
     assert L.lib.ronk_pcs_verify(None, d, d, d, d, C.byref(st)) == L.ERR_INVALID
+    # every other pointer of the host forms is required too, and is tested before the handle is read
+    assert L.lib.ronk_pcs_commit(d, None, d) == L.ERR_INVALID and L.lib.ronk_pcs_commit(d, d, None) == L.ERR_INVALID
+    assert L.lib.ronk_pcs_open(d, d, d, None, d, d, d, C.byref(st)) == L.ERR_INVALID
+    assert L.lib.ronk_pcs_open(d, d, d, d, d, d, d, None) == L.ERR_INVALID
+    assert L.lib.ronk_pcs_verify(d, d, None, d, d, C.byref(st)) == L.ERR_INVALID and L.lib.ronk_pcs_verify(d, d, d, d, d, None) == L.ERR_INVALID
+    assert st.value == 5
 
 
 SHAPES = [(6, 1, 2, 8, 2, 1, 1), (9, 3, 3, 8, 2, 5, 2), (12, 2, 4, 5, 3, 33, 3), (12, 3, 3, 64, 4, 16, 2), (20, 3, 5, 64, 4, 16, 2),

@@ -17,6 +17,7 @@ P_MID = PC.P_MID
 SRC = os.path.join(ROOT, "tests", "emu", "emu_accum.cpp")
 DEPS = [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("accum_kernels.h", "deep_kernels.h", "ext2_kernels.h", "ext2.h",
                                                                  "fri_kernels.h", "field_policy.h", "gl64.h", "mont64.h")]
+DEPS.append(os.path.join(ROOT, "tests", "emu", "emu_ref.h"))
 
 
 @pytest.fixture(scope="module")

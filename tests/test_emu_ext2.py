@@ -23,7 +23,7 @@ def emu():
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     exe = os.path.join(ROOT, "build", "emu_ext2")
     src = os.path.join(ROOT, "tests", "emu", "emu_ext2.cpp")
-    deps = [src] + [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_fri.cpp", "emu_poseidon.cpp")]
+    deps = [src] + [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_fri.cpp", "emu_poseidon.cpp", "emu_ref.h")]
     deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("ext2.h", "fri_kernels.h", "poseidon_kernels.h", "field_policy.h",
                                                                      "gl64.h", "mont64.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
@@ -38,7 +38,7 @@ def emu_device_form(emu):
     """the same emulator built with the HIP toolchain's clang++: mont64.h's `__clang__` branches, the device form of the carry
     chains (g++ compiles the portable form only)"""
     src = os.path.join(ROOT, "tests", "emu", "emu_ext2.cpp")
-    deps = [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_fri.cpp", "emu_poseidon.cpp")]
+    deps = [os.path.join(ROOT, "tests", "emu", f) for f in ("emu_fri.cpp", "emu_poseidon.cpp", "emu_ref.h")]
     deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("ext2.h", "fri_kernels.h", "poseidon_kernels.h", "field_policy.h",
                                                                      "gl64.h", "mont64.h")]
     return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_ext2_clang"), [src], deps)

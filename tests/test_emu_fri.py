@@ -21,7 +21,8 @@ def emu():
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     exe = os.path.join(ROOT, "build", "emu_fri")
     src = os.path.join(ROOT, "tests", "emu", "emu_fri.cpp")
-    deps = [src, os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp")]
+    deps = [src, os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp"),
+            os.path.join(ROOT, "tests", "emu", "emu_ref.h")]
     deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("fri_kernels.h", "poseidon_kernels.h", "field_policy.h", "gl64.h",
                                                                      "mont64.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
@@ -36,7 +37,8 @@ def emu_device_form(emu):
     """the same emulator built with the HIP toolchain's clang++: mont64.h's `__clang__` branches, the device form of the carry
     chains (g++ compiles the portable form only)"""
     src = os.path.join(ROOT, "tests", "emu", "emu_fri.cpp")
-    deps = [os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp")]
+    deps = [os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp"),
+            os.path.join(ROOT, "tests", "emu", "emu_ref.h")]
     deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("fri_kernels.h", "poseidon_kernels.h", "field_policy.h", "gl64.h",
                                                                      "mont64.h")]
     return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_fri_clang"), [src], deps)

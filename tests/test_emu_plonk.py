@@ -19,6 +19,7 @@ GL, MONT = 0xFFFFFFFF00000001, PC.MONT_P
 SRC = os.path.join(ROOT, "tests", "emu", "emu_plonk.cpp")
 DEPS = [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("plonk_kernels.h", "deep_kernels.h", "ext2_kernels.h", "ext2.h",
                                                                  "fri_kernels.h", "field_policy.h", "gl64.h", "mont64.h")]
+DEPS.append(os.path.join(ROOT, "tests", "emu", "emu_ref.h"))
 FIELDS = [(GL, 7, 7, 3), (GL, 7, 11, 2), (MONT, 10, 10, 1)]       # p, g, w, policies that serve it
 LANES, ROWS_GL, ROWS_MONT = 256, 4, 8
 FIRST_TWO_WORKGROUPS = (11, 12)                                  # log2 of the first M with more than LANES * rows rows, per policy

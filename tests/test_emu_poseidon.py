@@ -27,6 +27,7 @@ def _exe(name, flags):
     exe = os.path.join(ROOT, "build", name)
     src = os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp")
     deps = [src] + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("poseidon_kernels.h", "gl64.h", "mont64.h")]
+    deps.append(os.path.join(ROOT, "tests", "emu", "emu_ref.h"))
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         _build(["g++", "-O2", "-std=c++17"] + flags + ["-o", exe, src], exe)
     return exe
@@ -48,6 +49,7 @@ def emu_device_form(emu):
     chains (g++ compiles the portable form only)"""
     src = os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp")
     deps = [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("poseidon_kernels.h", "gl64.h", "mont64.h")]
+    deps.append(os.path.join(ROOT, "tests", "emu", "emu_ref.h"))
     return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_poseidon_clang"), [src], deps, opt="-O1")   # 4 s a run at -O0
 
 
