@@ -774,6 +774,58 @@ int ronk_pcs_open(const ronk_pcs* pcs, const uint64_t* M, const uint64_t* tree, 
                   const uint64_t* seed, uint64_t* proof, int* status);
 int ronk_pcs_verify(const ronk_pcs* pcs, const uint64_t* root, const uint64_t* z, const uint64_t* seed, const uint64_t* proof, int* status);
 
+/* ---- proof of work (grinding) on a Poseidon handle, stand-alone and as the step between FRI's commit phase and its query phase.
+ *      The reference has neither FRI nor grinding; the semantics are fixed here and restated on Python integers in tests/pow_ref.py.
+ *        word      pow_word(seed, n) = the first word of the one-shot sponge(seed || [n]) (seed: seed_len words, any 64-bit values,
+ *                  reduced on input), canonical -- exactly as FRI takes the word of a query index.
+ *        nonce     the SMALLEST n < 2^log2_limit with pow_word(seed, n) & (2^bits - 1) == 0; the word 2^64 - 1 when there is none;
+ *                  bits = 0 gives 0.  The bias of masking a word below p is ignored, as for the query indices.
+ *        search    a prefix launch (one lane: the permutations of the seed-only chunks, once) and ONE search launch of T lanes:
+ *                  lane g tries g, g + T, g + 2 T, ... and reloads the found word before every candidate; it stops at a candidate
+ *                  >= the found word or >= 2^log2_limit, and a hit lowers the found word by a 64-bit atomic minimum.  The result is
+ *                  the minimum whatever the execution order (csrc/pow_kernels.h has the argument).  T = max_lanes, or with
+ *                  max_lanes = 0 a quarter of the lanes the device keeps resident for the kernel (measured the fastest); never
+ *                  more than 2^log2_limit.  A candidate costs one permutation and no memory traffic; 2^bits candidates are expected.
+ *      ronk_pow_check (host integer logic, no device): the codes of the Poseidon handle's field (p < 2: RONK_ERR_INVALID, p = 2:
+ *      RONK_ERR_UNSUPPORTED, a composite p: RONK_ERR_NOT_PRIME), RONK_ERR_INVALID for rate = 0, then RONK_ERR_INVALID for
+ *      2^bits >= p or 2^log2_limit >= p (a nonce must be a canonical, distinct field element), then RONK_ERR_UNSUPPORTED for
+ *      bits > 40, log2_limit > 40 or seed_len > 4096.
+ *      The _dev calls are asynchronous on `stream`, use no library workspace and are legal under stream capture.  d_work:
+ *      ronk_pow_workspace_words words, caller-owned; d_nonce: one word.  ronk_pow_verify_dev writes *d_ok = 1 when *d_nonce is
+ *      < 2^log2_limit and meets the condition, else 0; it does not check minimality.  The host forms are synchronous; ronk_pow_grind
+ *      returns RONK_ERR_INDEX (and *nonce = 2^64 - 1) when nothing is found. */
+int ronk_pow_check(uint64_t p, uint32_t rate, size_t seed_len, uint32_t bits, uint32_t log2_limit);
+size_t ronk_pow_workspace_words(void);
+int ronk_pow_grind_dev(const ronk_poseidon* h, const uint64_t* d_seed, size_t seed_len, uint32_t bits, uint32_t log2_limit,
+                       size_t max_lanes, uint64_t* d_work, uint64_t* d_nonce, void* stream);
+int ronk_pow_verify_dev(const ronk_poseidon* h, const uint64_t* d_seed, size_t seed_len, uint32_t bits, uint32_t log2_limit,
+                        const uint64_t* d_nonce, int* d_ok, void* stream);
+int ronk_pow_grind(const ronk_poseidon* h, const uint64_t* seed, size_t seed_len, uint32_t bits, uint32_t log2_limit, size_t max_lanes,
+                   uint64_t* nonce);
+int ronk_pow_verify(const ronk_poseidon* h, const uint64_t* seed, size_t seed_len, uint32_t bits, uint32_t log2_limit, uint64_t nonce,
+                    int* ok);
+/* Grinding in FRI, both kinds of handle.  ronk_fri_set_pow is called before the handle is used; its codes are those of
+ * ronk_pow_check with seed_len = D, and bits = 0 restores the transcript above (byte-identical proofs, sizes and launches).  With
+ * bits > 0 the transcript becomes: u as above;  nonce = the grind of the seed u;  u' = sponge(u || [nonce]) squeezing D words;
+ * j_0 = sponge(u' || [q])[0] & (N_0 / A - 1).
+ *        proof     one word more, the nonce, APPENDED at the end: every offset above is unchanged.
+ *        workspace ronk_pow_workspace_words words more, at the end.
+ *        sizes     the size functions above take no handle: ronk_fri_handle_proof_words / ronk_fri_handle_workspace_words give
+ *                  the sizes of a handle, equal to theirs when bits = 0 (0 for a NULL handle).
+ *        verifier  reads the last proof word and sets status bit 64 when it is >= 2^log2_limit or fails the condition; u' and the
+ *                  indices are derived from the word as it stands (reduced on input), so every other check runs whatever this one
+ *                  finds.  ronk_fri_query_indices_dev follows the same rule.
+ *        prover    writes 2^64 - 1 when it finds nothing; ronk_fri_prove (host form) then returns RONK_ERR_INDEX.
+ * The batched commitment forwards: ronk_pcs_set_pow sets its FRI handle; the embedded FRI proof is one word longer, so the
+ * matrix-leaf section starts one word later; the openings follow FRI's indices; bit 64 passes through beside 8 / 16 / 32, and
+ * ronk_pcs_open (host form) returns RONK_ERR_INDEX when nothing is found. */
+int ronk_fri_set_pow(ronk_fri* fri, uint32_t bits, uint32_t log2_limit);
+size_t ronk_fri_handle_proof_words(const ronk_fri* fri);
+size_t ronk_fri_handle_workspace_words(const ronk_fri* fri);
+int ronk_pcs_set_pow(ronk_pcs* pcs, uint32_t bits, uint32_t log2_limit);
+size_t ronk_pcs_handle_proof_words(const ronk_pcs* pcs);
+size_t ronk_pcs_handle_workspace_words(const ronk_pcs* pcs);
+
 /* ---- the quadratic extension F_p[t] / (t^2 - w) of a 64-bit prime field: the reference's GaloisField<2, P>
  *      (src/algebra/field/extension/, arithmetic.rs, gf_101_2.rs; PlutoBaseFieldExtension is p = 101, w = 99 = -2).  An element
  *      is the pair (c0, c1) = c0 + c1 t, the reference's coeffs in increasing degree.  Arrays are PLANAR: n elements are [2][n]

@@ -205,6 +205,18 @@ _SIG = {
     "ronk_pcs_commit": (_int, [_vp, _vp, _vp]),
     "ronk_pcs_open": (_int, [_vp] * 7 + [C.POINTER(_int)]),
     "ronk_pcs_verify": (_int, [_vp] * 5 + [C.POINTER(_int)]),
+    "ronk_pow_check": (_int, [_u64, C.c_uint32, _sz, C.c_uint32, C.c_uint32]),
+    "ronk_pow_workspace_words": (_sz, []),
+    "ronk_pow_grind_dev": (_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _sz, _vp, _vp, _vp]),
+    "ronk_pow_verify_dev": (_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "ronk_pow_grind": (_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _sz, _pu]),
+    "ronk_pow_verify": (_int, [_vp, _vp, _sz, C.c_uint32, C.c_uint32, _u64, C.POINTER(_int)]),
+    "ronk_fri_set_pow": (_int, [_vp, C.c_uint32, C.c_uint32]),
+    "ronk_fri_handle_proof_words": (_sz, [_vp]),
+    "ronk_fri_handle_workspace_words": (_sz, [_vp]),
+    "ronk_pcs_set_pow": (_int, [_vp, C.c_uint32, C.c_uint32]),
+    "ronk_pcs_handle_proof_words": (_sz, [_vp]),
+    "ronk_pcs_handle_workspace_words": (_sz, [_vp]),
     "ronk_ext2_check": (_int, [_u64, _u64]),
     "ronk_ext2_vec_add_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "ronk_ext2_vec_sub_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -406,6 +418,12 @@ class PoseidonHandle:
     def sponge_dev(self, d_in, n_items, length, item_stride, elem_stride, d_out, n_out, stream=0):
         check(lib.ronk_poseidon_sponge_dev(self.h, d_in, n_items, length, item_stride, elem_stride, d_out, n_out, stream))
 
+    def pow_grind_dev(self, d_seed, seed_len, bits, log2_limit, max_lanes, d_work, d_nonce, stream=0):
+        check(lib.ronk_pow_grind_dev(self.h, d_seed, seed_len, bits, log2_limit, max_lanes, d_work, d_nonce, stream))
+
+    def pow_verify_dev(self, d_seed, seed_len, bits, log2_limit, d_nonce, d_ok, stream=0):
+        check(lib.ronk_pow_verify_dev(self.h, d_seed, seed_len, bits, log2_limit, d_nonce, d_ok, stream))
+
     def merkle_commit_dev(self, d_leaves, n_leaves, leaf_len, item_stride, elem_stride, digest_len, d_tree, stream=0):
         check(lib.ronk_merkle_commit_dev(self.h, d_leaves, n_leaves, leaf_len, item_stride, elem_stride, digest_len, d_tree, stream))
 
@@ -413,6 +431,12 @@ class PoseidonHandle:
                           d_ok, stream=0):
         check(lib.ronk_merkle_verify_dev(self.h, d_leaves, n_idx, leaf_len, item_stride, elem_stride, d_indices, d_paths, n_leaves,
                                          digest_len, d_root, d_ok, stream))
+
+
+def pow_default_limit(p, bits):
+    """log2_limit when the caller gives none: bits + 6 (a search that long fails with probability e^-64), capped by the library's
+    40 and by the field (2^log2_limit < p)"""
+    return min(bits + 6, 40, (p - 1).bit_length() - 1)
 
 
 def merkle_tree_words(n_leaves, digest_len):
@@ -433,7 +457,8 @@ class FriHandle:
     the challenges and the folded layers live in F_p[t] / (t^2 - w) (ronk_fri_create_ext): layers are planar [2][N], a challenge
     is two words, and input_ext says whether layer 0 is planar pairs too."""
 
-    def __init__(self, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, w=None, input_ext=False):
+    def __init__(self, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, w=None, input_ext=False,
+                 pow_bits=0, pow_log2_limit=None):
         self.h = _vp()
         self.pos = pos      # keeps the Poseidon handle alive
         self.ext, self.input_ext = w is not None, bool(input_ext)
@@ -452,6 +477,18 @@ class FriHandle:
             self.workspace_words = lib.ronk_fri_workspace_words_ext(*self.shape, int(self.input_ext))
         self.n, self.arity, self.digest_len = 1 << log2_n, 1 << log2_arity, digest_len
         self.input_words = self.n * (2 if self.input_ext else 1)
+        self.pow_bits = 0
+        if pow_bits:
+            self.set_pow(pow_bits, pow_log2_limit)
+
+    def set_pow(self, bits, log2_limit=None):
+        """grinding between the commit and the query phase (ronk_fri_set_pow), before the handle is used; bits = 0: none"""
+        if log2_limit is None:
+            log2_limit = pow_default_limit(self.pos.p, bits)
+        check(lib.ronk_fri_set_pow(self.h, bits, log2_limit))
+        self.pow_bits, self.pow_log2_limit = bits, log2_limit
+        self.proof_words = lib.ronk_fri_handle_proof_words(self.h)
+        self.workspace_words = lib.ronk_fri_handle_workspace_words(self.h)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -492,7 +529,8 @@ class PcsHandle:
     opened at n_points points of F_p[t] / (t^2 - w), on a PoseidonHandle, which it borrows.  The _dev methods take raw device
     pointers (int) and enqueue on `stream`; one call at a time per handle."""
 
-    def __init__(self, pos, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, n_columns, n_points):
+    def __init__(self, pos, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, n_columns, n_points,
+                 pow_bits=0, pow_log2_limit=None):
         self.h = _vp()
         self.pos = pos      # keeps the Poseidon handle alive
         check(lib.ronk_pcs_create(C.byref(self.h), pos.h, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries,
@@ -503,6 +541,18 @@ class PcsHandle:
         self.n, self.arity, self.digest_len = 1 << log2_n, 1 << log2_arity, digest_len
         self.columns, self.points, self.coeffs = n_columns, n_points, (1 << log2_n) >> log2_blowup
         self.tree_words = lib.ronk_merkle_tree_words(self.n >> log2_arity, digest_len)
+        self.pow_bits = 0
+        if pow_bits:
+            self.set_pow(pow_bits, pow_log2_limit)
+
+    def set_pow(self, bits, log2_limit=None):
+        """grinding in the embedded FRI (ronk_pcs_set_pow), before the handle is used; bits = 0: none"""
+        if log2_limit is None:
+            log2_limit = pow_default_limit(self.pos.p, bits)
+        check(lib.ronk_pcs_set_pow(self.h, bits, log2_limit))
+        self.pow_bits, self.pow_log2_limit = bits, log2_limit
+        self.proof_words = lib.ronk_pcs_handle_proof_words(self.h)
+        self.workspace_words = lib.ronk_pcs_handle_workspace_words(self.h)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:

@@ -337,6 +337,36 @@ class MerkleTree:
         return bool(ok[0])
 
 
+def pow_grind(sponge_params, seed, bits, log2_limit=None, max_lanes=0):
+    """The proof-of-work nonce of include/ronk_ntt.h ("proof of work"): the smallest n < 2^log2_limit (default bits + 6, capped by
+    the field) for which the first word of sponge(seed || [n]) has `bits` low zero bits.  sponge_params as for MerkleTree;
+    max_lanes = 0: the library's default.  RonkPanic(ERR_INDEX) when there is none."""
+    field = sponge_params[0]
+    handle = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
+    try:
+        s = L.arr([int(v) for v in seed])
+        if log2_limit is None:
+            log2_limit = L.pow_default_limit(field.ORDER, bits)
+        return L.out_scalar(L.lib.ronk_pow_grind, handle.h, L.ptr(s) if s.size else None, s.size, bits, log2_limit, max_lanes)
+    finally:
+        handle.close()
+
+
+def pow_verify(sponge_params, seed, bits, nonce, log2_limit=None):
+    """whether nonce < 2^log2_limit meets the condition of pow_grind (minimality is not checked)"""
+    field = sponge_params[0]
+    handle = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
+    try:
+        s = L.arr([int(v) for v in seed])
+        if log2_limit is None:
+            log2_limit = L.pow_default_limit(field.ORDER, bits)
+        ok = C.c_int(-1)
+        L.check(L.lib.ronk_pow_verify(handle.h, L.ptr(s) if s.size else None, s.size, bits, log2_limit, int(nonce), C.byref(ok)))
+        return bool(ok.value)
+    finally:
+        handle.close()
+
+
 class Fri:
     """The FRI prover and verifier of include/ronk_ntt.h ("FRI") for one column over a 64-bit field: `evals` are the values of a
     polynomial on the coset coset_shift * <omega_N>, N = 2^log2_n, natural order.  sponge_params as for MerkleTree.  With w, a
@@ -345,20 +375,23 @@ class Fri:
     soundness (the challenge field, the query count, the Poseidon constants) are the caller's concern."""
 
     def __init__(self, sponge_params, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, g=None, w=None,
-                 input_ext=False):
+                 input_ext=False, pow_bits=0, pow_log2_limit=None):
+        """pow_bits > 0: grinding between the commit and the query phase ("proof of work"); the nonce, searched below
+        2^pow_log2_limit (default pow_bits + 6, capped by the field), is the proof's last word"""
         field = sponge_params[0]
         self.field = field
         self.poseidon = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
         self.handle = L.FriHandle(self.poseidon, field._G if g is None else g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup,
-                                  n_queries, digest_len, w=w, input_ext=input_ext)
+                                  n_queries, digest_len, w=w, input_ext=input_ext, pow_bits=pow_bits, pow_log2_limit=pow_log2_limit)
         self.log2_n, self.log2_arity = log2_n, log2_arity
 
     def prove(self, evals, seed):
-        """-> the proof, ronk_fri_proof_words canonical words"""
+        """-> the proof, ronk_fri_handle_proof_words canonical words; RonkPanic(ERR_INDEX) when the grind finds no nonce"""
         return self.handle.prove(evals, seed)
 
     def verify(self, proof, seed):
-        """-> 0, or bits: 1 a Merkle path fails, 2 a fold mismatch, 4 the final layer is not of low degree"""
+        """-> 0, or bits: 1 a Merkle path fails, 2 a fold mismatch, 4 the final layer is not of low degree, 64 the nonce is out of
+        range or fails the proof-of-work condition"""
         return self.handle.verify(proof, seed)
 
     def fold(self, values, beta, layer=0):
@@ -398,12 +431,13 @@ class FriPcs:
     concern, and so is drawing the points after the commitment."""
 
     def __init__(self, sponge_params, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, columns, points,
-                 g=None):
+                 g=None, pow_bits=0, pow_log2_limit=None):
+        """pow_bits, pow_log2_limit: grinding in the embedded FRI, as for Fri"""
         field = sponge_params[0]
         self.field, self.w = field, w
         self.poseidon = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
         self.handle = L.PcsHandle(self.poseidon, field._G if g is None else g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup,
-                                  n_queries, digest_len, columns, points)
+                                  n_queries, digest_len, columns, points, pow_bits=pow_bits, pow_log2_limit=pow_log2_limit)
 
     def commit(self, matrix):
         """[columns][N] values -> the tree; root(tree) is the commitment"""
@@ -421,7 +455,7 @@ class FriPcs:
         return self.handle.open(matrix, tree, coeffs, z, seed)
 
     def verify(self, root, z, seed, proof):
-        """-> 0, or bits: 1 / 2 / 4 as FRI reports them, 8 a matrix path fails, 16 a DEEP mismatch, 32 a point on the domain"""
+        """-> 0, or bits: 1 / 2 / 4 / 64 as FRI reports them, 8 a matrix path fails, 16 a DEEP mismatch, 32 a point on the domain"""
         return self.handle.verify(root, z, seed, proof)
 
 

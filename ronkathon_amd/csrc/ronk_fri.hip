@@ -6,6 +6,7 @@
 #include "hip_launch.h"
 #include "poseidon_handle.h"
 #include "fri_kernels.h"
+#include "pow_kernels.h"
 #include "ext2_launch.h"
 
 // ------------------------------------------------------------------------------------- handle
@@ -22,6 +23,11 @@ struct ronk_fri {
   const u64* d_wfin = nullptr;
   FriLayer* d_layers = nullptr;
   u64* d_vs = nullptr;          // the verifier's state: the small words of FriShape, then ok [L][Q] ints
+  // grinding between the commit and the query phase (ronk_fri_set_pow); 0 bits: none, the launches,
+  // the proof and the workspace are those of a handle without it
+  u32 pow_bits = 0, pow_log2_limit = 0;
+  u64 proof_words() const { return sh.proof_words() + (pow_bits ? 1 : 0); }                     // the nonce is the last word
+  u64 workspace_words() const { return sh.workspace_words() + (pow_bits ? POW_WORK_WORDS : 0); }   // the prefix state, at the end
 };
 
 // the small state inside a workspace
@@ -280,6 +286,16 @@ extern "C" int ronk_fri_create_ext(ronk_fri** out, const ronk_poseidon* pos, uin
   return fri_create(out, pos, g, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, true, w, input_ext);
 }
 
+// grinding (include/ronk_ntt.h "proof of work"): set before the handle is used
+extern "C" int ronk_fri_set_pow(ronk_fri* h, uint32_t bits, uint32_t log2_limit) {
+  if (!h) return RONK_ERR_INVALID;
+  RCHK(ronk_pow_check(h->p, h->pos->rate, h->sh.d, bits, log2_limit));
+  h->pow_bits = bits; h->pow_log2_limit = log2_limit;
+  return RONK_OK;
+}
+extern "C" size_t ronk_fri_handle_proof_words(const ronk_fri* h) { return h ? (size_t)h->proof_words() : 0; }
+extern "C" size_t ronk_fri_handle_workspace_words(const ronk_fri* h) { return h ? (size_t)h->workspace_words() : 0; }
+
 // ------------------------------------------------------------------------------------- device entry points
 extern "C" int ronk_fri_fold_dev(const ronk_fri* h, uint32_t layer, const uint64_t* d_in, const uint64_t* d_beta, uint64_t* d_out,
                                  void* stream) {
@@ -348,6 +364,12 @@ extern "C" int ronk_fri_prove_dev(const ronk_fri* h, const uint64_t* d_evals, co
   u64* d_final = d_proof + L * D;
   HIPCHK(hipMemcpyAsync(d_final, vals[L], sh.vw(L) * sh.size(L) * 8, hipMemcpyDeviceToDevice, s));
   RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, L, L, d_final, s));
+  if (h->pow_bits) {
+    // grinding: the nonce of the seed u into the proof's last word, then u' = sponge(u || [nonce]) in the place of u
+    u64* d_nonce = d_proof + sh.proof_words();
+    RCHK(pow_grind_launch(h->pos, sm.u, (u32)D, h->pow_bits, h->pow_log2_limit, 0, d_work + sh.workspace_words(), d_nonce, s));
+    RCHK(pow_reseed_launch(h->pos, (u32)D, sm.u, h->pow_bits, h->pow_log2_limit, d_nonce, nullptr, s));
+  }
   // query phase: the indices, then every layer's leaves and paths
   RCHK(fri_indices_dev(h, sm, s));
   for (u32 l = 0; l < L; l++) {
@@ -372,6 +394,9 @@ extern "C" int ronk_fri_verify_dev(const ronk_fri* h, const uint64_t* d_proof, c
   const u64* d_final = d_proof + L * D;
   HIPCHK(hipMemsetAsync(d_status, 0, sizeof(int), s));
   RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, 0, L, d_final, s));
+  // the nonce as it stands: bit 64 when it is out of range or fails, and u' from it either way, so that every other check runs
+  if (h->pow_bits)
+    RCHK(pow_reseed_launch(h->pos, (u32)D, sm.u, h->pow_bits, h->pow_log2_limit, d_proof + sh.proof_words(), d_status, s));
   RCHK(fri_indices_dev(h, sm, s));
   for (u32 l = 0; l < L; l++)
     RCHK(ronk_merkle_verify_dev(h->pos, d_proof + sh.leaf_off(l), Q, sh.leaf_len(l), sh.leaf_len(l), 1, sm.idx + l * Q, d_proof + sh.path_off(l),
@@ -410,6 +435,8 @@ extern "C" int ronk_fri_query_indices_dev(const ronk_fri* h, const uint64_t* d_p
   const FriShape& sh = h->sh;
   const FriSmall sm(sh, h->d_vs);
   RCHK(fri_transcript_dev(h, sm, d_seed, d_proof, 0, sh.layers, d_proof + sh.layers * sh.d, s));
+  if (h->pow_bits)
+    RCHK(pow_reseed_launch(h->pos, (u32)sh.d, sm.u, h->pow_bits, h->pow_log2_limit, d_proof + sh.proof_words(), nullptr, s));
   RCHK(fri_indices_dev(h, sm, s));
   HIPCHK(hipMemcpyAsync(d_indices, sm.idx, sh.queries * 8, hipMemcpyDeviceToDevice, s));   // layer 0: j_0 mod m_0 = j_0
   return RONK_OK;
@@ -422,10 +449,11 @@ extern "C" int ronk_fri_prove(const ronk_fri* h, const uint64_t* evals, const ui
   const FriShape& sh = h->sh;
   HostCall hc;
   const u64 *de = hc.in(evals, sh.vw(0) * sh.size(0)), *ds = hc.in(seed, sh.d);
-  u64 *dw = hc.out(sh.workspace_words()), *dp = hc.out(sh.proof_words());
+  u64 *dw = hc.out(h->workspace_words()), *dp = hc.out(h->proof_words());
   RCHK(hc.rc);
   RCHK(ronk_fri_prove_dev(h, de, ds, dw, dp, nullptr));
-  return hc.get(proof, dp, sh.proof_words() * 8);
+  RCHK(hc.get(proof, dp, h->proof_words() * 8));
+  return h->pow_bits && proof[sh.proof_words()] == POW_NONE ? RONK_ERR_INDEX : RONK_OK;   // the search found nothing below the limit
 }
 
 extern "C" int ronk_fri_verify(const ronk_fri* h, const uint64_t* proof, const uint64_t* seed, int* status) {
@@ -433,7 +461,7 @@ extern "C" int ronk_fri_verify(const ronk_fri* h, const uint64_t* proof, const u
   RCHK(need_device());
   const FriShape& sh = h->sh;
   HostCall hc;
-  const u64 *dp = hc.in(proof, sh.proof_words()), *ds = hc.in(seed, sh.d);
+  const u64 *dp = hc.in(proof, h->proof_words()), *ds = hc.in(seed, sh.d);
   u64* dst = hc.out(1);
   RCHK(hc.rc);
   RCHK(ronk_fri_verify_dev(h, dp, ds, (int*)dst, nullptr));

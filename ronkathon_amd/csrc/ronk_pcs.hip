@@ -8,6 +8,7 @@
 #include "poseidon_handle.h"
 #include "ext2_launch.h"
 #include "deep_kernels.h"
+#include "pow_kernels.h"
 
 // ------------------------------------------------------------------------------------- handle
 struct ronk_pcs {
@@ -23,11 +24,12 @@ struct ronk_pcs {
   u64* d_vs = nullptr;          // the verifier's state: a [D], ok [Q] ints
   u64 leaf_len() const { return (u64)C << sh.eta; }
   u64 claims() const { return 2 * (u64)K * C; }
-  u64 fri_proof() const { return sh.proof_words(); }
+  u32 pow_bits = 0;             // the FRI handle's grinding bits (ronk_pcs_set_pow): its proof and workspace grow with them
+  u64 fri_proof() const { return sh.proof_words() + (pow_bits ? 1 : 0); }
   u64 proof_words() const { return claims() + fri_proof() + sh.queries * leaf_len() + sh.queries * sh.log2m(0) * sh.d; }
   // a [D], open status [Q], G [2][N], then the FRI workspace (which holds the query indices)
   u64 small_words() const { return sh.d + sh.queries; }
-  u64 workspace_words() const { return small_words() + 2 * sh.size(0) + sh.workspace_words(); }
+  u64 workspace_words() const { return small_words() + 2 * sh.size(0) + sh.workspace_words() + (pow_bits ? POW_WORK_WORDS : 0); }
 };
 
 // run the statement with KK bound to the number of points ...
@@ -237,6 +239,16 @@ extern "C" int ronk_pcs_create(ronk_pcs** out, const ronk_poseidon* pos, uint64_
   return RONK_OK;
 }
 
+// grinding: the owned FRI handle does it; this handle only follows its sizes
+extern "C" int ronk_pcs_set_pow(ronk_pcs* h, uint32_t bits, uint32_t log2_limit) {
+  if (!h) return RONK_ERR_INVALID;
+  RCHK(ronk_fri_set_pow(h->fri, bits, log2_limit));
+  h->pow_bits = bits;
+  return RONK_OK;
+}
+extern "C" size_t ronk_pcs_handle_proof_words(const ronk_pcs* h) { return h ? (size_t)h->proof_words() : 0; }
+extern "C" size_t ronk_pcs_handle_workspace_words(const ronk_pcs* h) { return h ? (size_t)h->workspace_words() : 0; }
+
 // ------------------------------------------------------------------------------------- device entry points
 static int eval_batch_launch(const Ext2Launch& c, const u64* d_coef, u32 C, u64 d, const u64* d_z, u32 K, u64* d_y, hipStream_t s) {
   EXT2_DISPATCH3(c, hipLaunchKernelGGL((deep_eval_kernel<FF>), dim3(C), dim3(DEEP_EVAL_LANES), 0, s, c.k, c.w, d_coef, d, d_z, K, C, d_y));
@@ -381,7 +393,9 @@ extern "C" int ronk_pcs_open(const ronk_pcs* h, const uint64_t* M, const uint64_
   RCHK(hc.rc);
   RCHK(ronk_pcs_open_dev(h, dm, dt, dc, dz, ds, dw, dp, (int*)dst, nullptr));
   RCHK(hc.get(proof, dp, h->proof_words() * 8));
-  return hc.get(status, dst, sizeof(int));
+  RCHK(hc.get(status, dst, sizeof(int)));
+  // the FRI proof's last word: the search found nothing below the limit
+  return h->pow_bits && proof[h->claims() + sh.proof_words()] == POW_NONE ? RONK_ERR_INDEX : RONK_OK;
 }
 
 extern "C" int ronk_pcs_verify(const ronk_pcs* h, const uint64_t* root, const uint64_t* z, const uint64_t* seed, const uint64_t* proof,

@@ -54,6 +54,13 @@ int newton_ladder_dev(const FieldCtx& fld, u64 G, const u64* f, size_t Lp, u64* 
 //      left j_0 of every query, in stream order (ronk_pcs.hip reads it instead of replaying the transcript)
 const u64* fri_handle_indices(const ronk_fri* h);
 
+// ---- proof of work (ronk_pow.hip), arguments already checked: the prefix and the search launch (d_work: ronk_pow_workspace_words
+//      words, *d_nonce receives the nonce or 2^64 - 1; max_lanes = 0: the resident lanes), and the step FRI takes after it:
+//      d_u <- sponge(d_u || [*d_nonce]) squeezing d words, with d_status bit 64 ORed in when the nonce is out of range or fails
+int pow_grind_launch(const ronk_poseidon* h, const u64* d_seed, u32 seed_len, u32 bits, u32 log2_limit, u64 max_lanes, u64* d_work,
+                     u64* d_nonce, hipStream_t s);
+int pow_reseed_launch(const ronk_poseidon* h, u32 d, u64* d_u, u32 bits, u32 log2_limit, const u64* d_nonce, int* d_status, hipStream_t s);
+
 // ---- host integer logic
 typedef unsigned __int128 u128;
 static inline u64 h_mulmod(u64 a, u64 b, u64 p) { return (u64)(((u128)a * b) % p); }
