@@ -910,6 +910,54 @@ int ronk_perm_product(uint64_t p, uint64_t w, const uint64_t* wires, const uint6
 int ronk_logup_sum(uint64_t p, uint64_t w, const uint64_t* vals, const uint64_t* mult, uint32_t n_columns, size_t n,
                    const uint64_t* alpha, uint64_t* S, uint64_t* last, int* status);
 
+/* ---- lookup multiplicities and the logUp quotient: the two steps either side of ronk_logup_sum_dev that make the running sum a
+ *      complete, checkable lookup argument.  The reference has no prover; the semantics are fixed here and restated on Python
+ *      integers in tests/lookup_ref.py.  Field: any odd prime p < 2^64, as for the base-field scans above.
+ *        multiplicities   d_table [T] and d_vals [C][n] (row-major) are any 64-bit words; every comparison is between the words
+ *                  REDUCED mod p, so 3 and p + 3 are equal.  Table entry j is the representative of its value when no smaller
+ *                  index holds the same value.  d_mult [T], canonical: at a representative, the number of pairs (c, i) with
+ *                  f_c[i] = t[j], taken mod p, or with negate = 1 p minus that (0 stays 0); at every other j, 0.  With negate = 1
+ *                  it is exactly the m row ronk_logup_sum_dev wants for the table column.  d_missing (required, two words): [0]
+ *                  the number of pairs (c, i) whose value is not in the table, [1] the smallest c n + i among them, or 2^64 - 1
+ *                  when there is none.  Every word written is a function of the inputs alone, whatever the scheduling.
+ *                  T, n <= 2^28, C <= 16.  d_work: ronk_lookup_workspace_words(T) words, caller-owned (an open-addressing table of
+ *                  the power-of-two capacity >= 2 T, two words per slot); 0 for T = 0 or T > 2^28.  Outputs must not overlap
+ *                  inputs or each other.
+ *      Errors, in this order and before a device is needed: NULL pointer, T = 0, n = 0 or C = 0: RONK_ERR_INVALID; T or n > 2^28
+ *      or C > 16: RONK_ERR_UNSUPPORTED; p < 2 RONK_ERR_INVALID, p = 2 RONK_ERR_UNSUPPORTED, else the code of ronk_check_prime;
+ *      negate other than 0 or 1: RONK_ERR_INVALID.  ronk_lookup_check (host-side integer logic) reports those of the shape and
+ *      the field.  The _dev call is asynchronous on `stream`: FOUR kernel launches (clear, build, count, finalise), integer atomics
+ *      and launch boundaries only -- no lane or workgroup ever waits for another, every probe loop is bounded by the capacity --
+ *      no host round trip, no library workspace: legal under stream capture.
+ *        logUp quotient   on the domain of a ronk_plonk handle (below: N, B, M, x_i; its label multipliers are unused).  Inputs on
+ *                  the coset, any 64-bit words: d_vals [C][M]; d_mult [C][M] or NULL for all ones; d_S planar [2][M], each plane
+ *                  the extension of one plane of what ronk_logup_sum_dev wrote; d_alpha the logUp challenge (two words);
+ *                  d_lambda two extension elements lambda0, lambda1 (four words), the powers of the quotient challenge this
+ *                  constraint pair receives; d_T_in planar [2][M] or NULL for zero.
+ *        row i     D_c = alpha + v_c[i];  P = prod_c D_c;  Q = sum_c m_c[i] prod_(c' != c) D_c'
+ *                  R = (S_((i + B) mod M) - S_i) P - Q
+ *                  T_out_i = T_in_i + lambda0 R / (x_i^N - 1) + lambda1 S_i / (N (x_i - 1))
+ *                  The last term is lambda1 S L1 / (x^N - 1); nothing is divided by D_c and there is no status word.
+ *        output    d_T_out planar [2][M], canonical.  d_T_out == d_T_in is allowed (row i reads T_in at row i only); it must not
+ *                  overlap S, the values or the multiplicities.
+ *      The caller's concern: the transition holds on every row of H only when S[N] = 0, that is when d_last of
+ *      ronk_logup_sum_dev is zero; and T is a polynomial of degree below M only when C <= B (its coefficients from C N - C upward
+ *      then vanish).  Errors: NULL pointer (d_mult and d_T_in excepted) or C = 0: RONK_ERR_INVALID; C > 16: RONK_ERR_UNSUPPORTED.
+ *      One kernel launch, legal under stream capture.  The host-pointer forms are synchronous and allocate their own workspace.
+ *      (ronk_plonk is declared with the PLONK quotient below.) */
+struct ronk_plonk;
+size_t ronk_lookup_workspace_words(size_t n_table);
+int ronk_lookup_check(uint64_t p, size_t n_table, uint32_t n_columns, size_t n);
+int ronk_lookup_mult_dev(uint64_t p, const uint64_t* d_table, size_t n_table, const uint64_t* d_vals, uint32_t n_columns, size_t n,
+                         int negate, uint64_t* d_mult, uint64_t* d_missing, uint64_t* d_work, void* stream);
+int ronk_lookup_mult(uint64_t p, const uint64_t* table, size_t n_table, const uint64_t* vals, uint32_t n_columns, size_t n, int negate,
+                     uint64_t* mult, uint64_t* missing);
+int ronk_logup_quotient_dev(const struct ronk_plonk* h, const uint64_t* d_vals, const uint64_t* d_mult, uint32_t n_columns,
+                            const uint64_t* d_S, const uint64_t* d_alpha, const uint64_t* d_lambda, const uint64_t* d_T_in,
+                            uint64_t* d_T_out, void* stream);
+int ronk_logup_quotient(const struct ronk_plonk* h, const uint64_t* vals, const uint64_t* mult, uint32_t n_columns, const uint64_t* S,
+                        const uint64_t* alpha, const uint64_t* lambda, const uint64_t* T_in, uint64_t* T_out);
+
 /* ---- PLONK quotient: the quotient polynomial of a three-wire PLONK circuit on the evaluation coset, in ONE kernel launch.  The
  *      gate equation is the reference's a QL + b QR + a b QM + o QO + QC = 0 (src/compiler/program.rs:4-5,
  *      CommonPreprocessedInput); the reference has no prover, so the semantics are fixed here and restated on Python integers in

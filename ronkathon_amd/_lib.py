@@ -246,6 +246,12 @@ _SIG = {
     "ronk_ext2_vec_prefix_sum": (_int, [_u64, _u64, _vp, _vp, _sz, _int, _vp]),
     "ronk_perm_product": (_int, [_u64, _u64, _vp, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, _vp, C.POINTER(_int)]),
     "ronk_logup_sum": (_int, [_u64, _u64, _vp, _vp, C.c_uint32, _sz, _vp, _vp, _vp, C.POINTER(_int)]),
+    "ronk_lookup_workspace_words": (_sz, [_sz]),
+    "ronk_lookup_check": (_int, [_u64, _sz, C.c_uint32, _sz]),
+    "ronk_lookup_mult_dev": (_int, [_u64, _vp, _sz, _vp, C.c_uint32, _sz, _int, _vp, _vp, _vp, _vp]),
+    "ronk_lookup_mult": (_int, [_u64, _vp, _sz, _vp, C.c_uint32, _sz, _int, _vp, _vp]),
+    "ronk_logup_quotient_dev": (_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ronk_logup_quotient": (_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "ronk_plonk_check": (_int, [_u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
     "ronk_plonk_create": (_int, [C.POINTER(_vp), _u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
     "ronk_plonk_destroy": (_int, [_vp]),

@@ -547,3 +547,42 @@ def plonk_quotient(field, g, w, log2_n, log2_blowup, coset_shift, wires, sel, si
     finally:
         L.lib.ronk_plonk_destroy(h)
     return T
+
+
+def lookup_multiplicities(field, table, vals, negate=False):
+    """The multiplicities of the lookup columns vals [columns][n] in table [T] (any 64-bit words, compared mod p): -> (mult [T],
+    missing_count, first_missing).  mult[j] is the number of cells equal to table[j], mod p (p minus that with negate: the m row
+    logup_sum takes for the table column), at the smallest index of each table value and 0 at its repeats; missing_count the
+    number of cells whose value is not in the table and first_missing the smallest flat index c * n + i among them, or None
+    (include/ronk_ntt.h "lookup multiplicities and the logUp quotient")."""
+    t = L.arr(table).ravel()
+    v = _columns("vals", vals)
+    if t.size == 0:
+        raise L.RonkPanic(L.ERR_INVALID, "the table holds at least one word")
+    mult, missing = np.empty(t.size, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+    L.check(L.lib.ronk_lookup_mult(field.ORDER, L.ptr(t), t.size, L.ptr(v), v.shape[0], v.shape[1], int(bool(negate)), L.ptr(mult),
+                                   L.ptr(missing)))
+    return mult, int(missing[0]), None if int(missing[1]) == 2**64 - 1 else int(missing[1])
+
+
+def logup_quotient(field, g, w, log2_n, log2_blowup, coset_shift, vals, mult, S, alpha, lam, T_in=None):
+    """The logUp constraints on the coset of plonk_quotient: vals and mult [columns][M] (mult None: all ones), S planar [2][M], alpha
+    a pair, lam the two pairs (lambda0, lambda1), T_in planar [2][M] or None.  -> T_in + lambda0 R / (x^N - 1) + lambda1 S /
+    (N (x - 1)) row by row, planar [2][M], with R = (S_(i+B) - S_i) prod_c D_c - sum_c m_c prod_(c' != c) D_c', D_c = alpha + v_c."""
+    M = 1 << (log2_n + log2_blowup)
+    v = _columns("vals", vals)
+    m = None if mult is None else _columns("mult", mult, v)
+    s = _columns("S", S)
+    t = None if T_in is None else _columns("T_in", T_in, s)
+    al, la = L.arr([int(c) for c in alpha]), L.arr([int(c) for e in lam for c in e])
+    if v.shape[1] != M or s.shape != (2, M) or al.size != 2 or la.size != 4:
+        raise L.RonkPanic(L.ERR_INVALID, "vals [columns][M], S [2][M], alpha a pair, lam two pairs")
+    h = C.c_void_p()
+    L.check(L.lib.ronk_plonk_create(C.byref(h), field.ORDER, g, w, log2_n, log2_blowup, coset_shift, (C.c_uint64 * 3)(1, 2, 3)))
+    try:
+        T = np.empty(2 * M, dtype=np.uint64)
+        L.check(L.lib.ronk_logup_quotient(h, L.ptr(v), None if m is None else L.ptr(m), v.shape[0], L.ptr(s), L.ptr(al), L.ptr(la),
+                                          None if t is None else L.ptr(t), L.ptr(T)))
+    finally:
+        L.lib.ronk_plonk_destroy(h)
+    return T

@@ -5,16 +5,7 @@
 #include "hip_launch.h"
 #include "ext2_launch.h"
 #include "plonk_kernels.h"
-
-struct ronk_plonk {
-  u64 p = 0;
-  u32 log2m = 0;
-  Ext2Launch c;            // the field policy, its constants, W
-  DeepDomain dm{};
-  PlonkTab tab{};
-  u64* d_dom = nullptr;    // lo, hi of the domain
-  u64* d_vinv = nullptr;   // the B inverses of the vanishing polynomial
-};
+#include "plonk_handle.h"
 
 extern "C" int ronk_plonk_check(uint64_t p, uint64_t g, uint64_t w, uint32_t log2_n, uint32_t log2_blowup, uint64_t coset_shift,
                                 const uint64_t k[3]) {
