@@ -4,7 +4,7 @@ ARCH ?= gfx950
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude
 CSRC = ronkathon_amd/csrc
 LIB = ronkathon_amd/libronk_ntt.so
-OBJS = build/tile_kernels_wl.o build/tile_kernels_r4.o build/tile_kernels_mont.o build/tile_kernels_mont_feat.o build/tile_kernels_mont_mul.o build/tile_kernels.o build/tile_kernels_cfg.o build/tile_kernels_half.o build/tile_kernels_feat.o build/tile_kernels_mul.o build/tile_kernels_dist_mul.o build/small_kernels.o build/ronk_core.o build/ronk_plan.o build/ronk_callers.o build/ronk_dist.o build/ronk_msm.o build/ronk_recover.o build/ronk_multipoint.o build/ronk_hash.o build/ronk_fr_ntt.o build/ronk_fri.o build/ronk_ext2.o build/ronk_pcs.o build/ronk_accum.o build/ronk_plonk.o build/ronk_pow.o build/ronk_lookup.o
+OBJS = build/tile_kernels_wl.o build/tile_kernels_r4.o build/tile_kernels_mont.o build/tile_kernels_mont_feat.o build/tile_kernels_mont_mul.o build/tile_kernels.o build/tile_kernels_cfg.o build/tile_kernels_half.o build/tile_kernels_feat.o build/tile_kernels_mul.o build/tile_kernels_dist_mul.o build/small_kernels.o build/ronk_core.o build/ronk_plan.o build/ronk_callers.o build/ronk_workspace.o build/ronk_dist.o build/ronk_msm.o build/ronk_recover.o build/ronk_multipoint.o build/ronk_hash.o build/ronk_fr_ntt.o build/ronk_fri.o build/ronk_ext2.o build/ronk_pcs.o build/ronk_accum.o build/ronk_plonk.o build/ronk_pow.o build/ronk_lookup.o
 HDRS = $(wildcard $(CSRC)/*.h) include/ronk_ntt.h
 
 all: $(LIB) oracle

@@ -1,221 +1,12 @@
 // ronk_callers.hip -- C ABI of libronk_ntt.so, part 3: the callers either side of the transform:
 // evaluate, division (kzg::open), Lagrange evaluate, Reed-Solomon encode / decode, KZG commit (curve MSM).
-#include "runtime.h"
+#include "workspace.h"
 #include "scan_kernels.h"
 #include "lindiv_kernels.h"
 #include "interp_kernels.h"
 #include "curve_kernels.h"
 
 // ------------------------------------------------------------------------------ evaluate / divrem / RS
-// Workspace pool for the scan entry points: hipMalloc'd buffers, each guarded by a completion event, so a call
-// never synchronises the device and never frees memory that queued work still uses.  A slot is reused when its
-// last work has completed or was queued on the same stream (stream order then protects it).  (hipMallocAsync /
-// hipFreeAsync were tried first and dropped: on ROCm 7.2 / gfx950 a kernel intermittently read stale data from
-// a pool block reused across calls -- 4 of 12 test runs -- while plain allocations never did.)
-struct WsSlot {
-  void* p = nullptr;
-  u32* ctl = nullptr;   // 64 bytes of control words, ZERO whenever the slot is not in use (fused scan kernels)
-  u64* lb = nullptr;    // two look-back arrays of LB_WORDS entries (scan_kernels.h, one-launch forms): the one a call uses
-  u32 lb_calls = 0;     // was set to LB_EMPTY by the call before it (at creation: both), parity = lb_calls & 1
-  size_t bytes = 0;
-  int device = -1;
-  hipEvent_t done = nullptr;
-  hipStream_t last = nullptr;
-  bool used = false;   // ever had work queued
-  bool busy = false;   // leased right now
-  bool ev_valid = false;   // `done` was recorded behind the slot's last work
-  bool oneoff = false;     // larger than WS_CACHE_MAX: never pooled, freed once its work has completed
-};
-static std::mutex g_ws_mu;
-static std::vector<WsSlot*> g_ws;
-// Retention bound: the pool keeps what the scans, the decode and ordinary divisions need (64 KiB .. 256 MiB per slot, a power
-// of two each).  Anything larger -- the ~10 x Lp x 8 bytes of a 2^27 Newton division, 16 GiB after rounding -- is a ONE-OFF
-// allocation of exactly the requested size: on release it goes to g_ws_grave with an event behind its last work and is freed
-// by the next acquire / ronk_trim_workspace() that finds the event complete (never while queued work still uses it).
-static constexpr size_t WS_CACHE_MAX = (size_t)256 << 20;
-static std::vector<WsSlot*> g_ws_grave;
-static void ws_free_slot(WsSlot* w) {
-  if (w->p) (void)hipFree(w->p);
-  if (w->ctl) (void)hipFree(w->ctl);
-  if (w->lb) (void)hipFree(w->lb);
-  if (w->done) (void)hipEventDestroy(w->done);
-  delete w;
-}
-// g_ws_mu held.  wait = false: free what has completed; true: wait for the rest (ronk_trim_workspace).
-static void ws_reap(bool wait) {
-  for (size_t i = 0; i < g_ws_grave.size();) {
-    WsSlot* w = g_ws_grave[i];
-    bool done = !w->ev_valid || hipEventQuery(w->done) == hipSuccess;
-    if (!done && wait) done = hipEventSynchronize(w->done) == hipSuccess;
-    if (!done) { (void)hipGetLastError(); i++; continue; }
-    ws_free_slot(w);
-    g_ws_grave[i] = g_ws_grave.back();
-    g_ws_grave.pop_back();
-  }
-}
-// Completion events are recorded only once the pool has been seen from a second stream: while every call comes from ONE
-// stream, stream order protects a reused slot and the hipEventRecord per call (~1.5 us of the 12.5 us an evaluate of 2^22
-// coefficients takes end to end) buys nothing.  The stream that triggers the switch simply gets a fresh slot.
-static bool g_ws_multi = false;
-struct WsLease {
-  WsSlot* slot = nullptr;
-  hipStream_t s = nullptr;
-  ~WsLease() {
-    if (!slot) return;
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    if (slot->oneoff) {   // never pooled: an event behind its work, freed by whoever finds it complete
-      // A capturing stream: an event recorded inside a capture never completes for hipEventQuery / hipEventSynchronize, so the
-      // buffer would sit in the grave for ever (through ronk_trim_workspace as well).  A captured graph may be replayed long
-      // after this call returned, so its one-off workspace cannot be freed at all while the graph lives: acquire() refuses
-      // one-off workspaces under capture (RONK_ERR_UNSUPPORTED); should one get here regardless, it is kept, not leaked
-      // silently: the grave entry has no event and is freed by the next reap.
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-      if (cap != hipStreamCaptureStatusNone) {
-        slot->ev_valid = false;
-      } else {
-        slot->ev_valid = hipEventRecord(slot->done, s) == hipSuccess;
-        if (!slot->ev_valid) { (void)hipGetLastError(); (void)hipStreamSynchronize(s); }
-      }
-      slot->busy = false;
-      g_ws_grave.push_back(slot);
-      ws_reap(false);
-      return;
-    }
-    // (a capturing stream leaves no event: one recorded inside a capture never completes for the pool's queries; the slot stays
-    //  tied to the stream it was last used on -- the captured graph's stream -- and other streams wait for the device instead)
-    hipStreamCaptureStatus capr = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &capr) != hipSuccess) { (void)hipGetLastError(); capr = hipStreamCaptureStatusNone; }
-    slot->ev_valid = capr == hipStreamCaptureStatusNone && g_ws_multi && hipEventRecord(slot->done, s) == hipSuccess;
-    slot->last = s; slot->used = true; slot->busy = false;
-  }
-  int acquire(size_t bytes, hipStream_t st) {
-    s = st;
-    size_t need = 65536;
-    while (need < bytes) need <<= 1;
-    const bool oneoff = need > WS_CACHE_MAX;
-    if (oneoff) need = (bytes + 255) & ~(size_t)255;   // exactly what was asked for, not the next power of two
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (oneoff) {   // (see ~WsLease: a captured graph would use the buffer after it has been freed)
-      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-      if (cap != hipStreamCaptureStatusNone) return RONK_ERR_UNSUPPORTED;
-    }
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    ws_reap(false);
-    size_t on_dev = 0;
-    WsSlot* waitable = nullptr;
-    for (WsSlot* w : g_ws) {
-      if (oneoff) break;
-      if (w->device != dev) continue;
-      on_dev++;
-      if (w->busy || w->bytes < need) continue;
-      if (!w->used || w->last == st || (w->ev_valid && hipEventQuery(w->done) == hipSuccess)) { slot = w; break; }
-      g_ws_multi = true;                        // a slot last used by ANOTHER stream: from now on every release leaves an event
-      if (!waitable) waitable = w;
-    }
-    if (!slot && waitable && on_dev >= 32) {  // bound the pool: wait for an old slot instead of growing
-      // A slot released before the pool went multi-stream has no event, and its stream handle cannot be trusted any more (a
-      // destroyed hipStream_t crashes hipEventRecord / hipStreamSynchronize -- tests/test_gpu_parity.py destroys one on
-      // purpose), so the one thing left to wait on is the device: the slot's device IS the current one (filter above).
-      // At most once per process and device: from the switch on every release records its event.
-      if (waitable->ev_valid) (void)hipEventSynchronize(waitable->done);
-      else (void)hipDeviceSynchronize();
-      slot = waitable;
-    }
-    if (!slot) {
-      // A capturing stream may not be handed a FRESH slot: creating one needs hipMalloc and the look-back fills, which either
-      // invalidate a global-mode capture (legacy null-stream calls) or would become nodes of the caller's graph.  The caller
-      // warms the pool with one call of the same shape outside the capture (include/ronk_ntt.h); until then the captured call
-      // is refused, never half-initialised.
-      hipStreamCaptureStatus capn = hipStreamCaptureStatusNone;
-      if (hipStreamIsCapturing(st, &capn) != hipSuccess) { (void)hipGetLastError(); capn = hipStreamCaptureStatusNone; }
-      if (capn != hipStreamCaptureStatusNone) {
-        (void)hip_fail(hipErrorStreamCaptureUnsupported, "workspace: no warm pool slot for a capturing stream (call once outside the capture first)");
-        return RONK_ERR_UNSUPPORTED;
-      }
-      WsSlot* w = new WsSlot();
-      w->oneoff = oneoff;
-      hipError_t e = hipMalloc(&w->p, need);
-      if (e == hipErrorOutOfMemory && !g_ws_grave.empty()) {
-        // two back-to-back large divisions on one stream: the first one's one-off buffer (gigabytes) is still in the grave
-        // behind its event -- wait for the grave instead of reporting out-of-memory, then try once more
-        (void)hipGetLastError();
-        ws_reap(true);
-        e = hipMalloc(&w->p, need);
-      }
-      // The initial fills are ordered on the ACQUIRING stream: hipMemset runs on the null stream and returns before it has
-      // executed, so a kernel launched right afterwards on a NON-BLOCKING stream could read the look-back arrays before they
-      // were filled -- and take garbage for a published chunk sum (found by the four-thread fuzz sweep, round 5: one evaluate
-      // in ~5 000 threaded cases, always on a caller-created stream and a fresh slot).  A later user on another stream gets
-      // the slot only behind its completion event (or the device drain of the first cross-stream use), i.e. behind the fills.
-      // (A capturing stream never gets here: refused above.)
-      const bool on_st = true;
-      if (e == hipSuccess) e = hipMalloc((void**)&w->ctl, 64);
-      if (e == hipSuccess) e = on_st ? hipMemsetAsync(w->ctl, 0, 64, st) : hipMemset(w->ctl, 0, 64);
-      if (e == hipSuccess) e = hipMalloc((void**)&w->lb, (size_t)2 * LB_WORDS * 8);
-      if (e == hipSuccess) e = on_st ? hipMemsetAsync(w->lb, 0xFF, (size_t)2 * LB_WORDS * 8, st)
-                                     : hipMemset(w->lb, 0xFF, (size_t)2 * LB_WORDS * 8);   // LB_EMPTY everywhere
-      if (e == hipSuccess) e = hipEventCreateWithFlags(&w->done, hipEventDisableTiming);
-      if (e != hipSuccess) { if (w->p) (void)hipFree(w->p); if (w->ctl) (void)hipFree(w->ctl); if (w->lb) (void)hipFree(w->lb); delete w; return hip_fail(e, "workspace"); }
-      w->bytes = need; w->device = dev;
-      if (!oneoff) g_ws.push_back(w);
-      slot = w;
-    }
-    slot->busy = true;
-    return RONK_OK;
-  }
-  u64* u() const { return (u64*)slot->p; }
-  u32* ctl() const { return slot->ctl; }
-  // look-back arrays of a one-launch scan: *cur is all LB_EMPTY now, *next is cleared by the kernel for the call after
-  // The parity advances only through lb_commit(), AFTER the launch was accepted: a failed launch never ran the kernel that
-  // clears *next, so the same (still clean) *cur must serve the following call.
-  void lb_arrays(u64** cur, u64** next) {
-    const u32 par = slot->lb_calls & 1;
-    *cur = slot->lb + (size_t)par * LB_WORDS;
-    *next = slot->lb + (size_t)(par ^ 1) * LB_WORDS;
-  }
-  void lb_commit() { slot->lb_calls++; }
-};
-// The pool for other translation units (runtime.h): one lease, released (event behind the work queued on `s`) by ws_lease_release
-int ws_lease_acquire(size_t bytes, hipStream_t s, void** lease, u64** ptr) {
-  WsLease* w = new WsLease();
-  const int rc = w->acquire(bytes, s);
-  if (rc != RONK_OK) { delete w; return rc; }
-  *lease = w;
-  *ptr = w->u();
-  return RONK_OK;
-}
-void ws_lease_release(void* lease) { delete (WsLease*)lease; }
-// Releases every idle pool slot and every finished one-off buffer (include/ronk_ntt.h).  Waits for the work behind them
-// (events; a slot released in single-stream mode has none: its device is synchronised).
-extern "C" int ronk_trim_workspace(void) {
-  std::lock_guard<std::mutex> lk(g_ws_mu);
-  ws_reap(true);
-  int cur = -1;
-  (void)hipGetDevice(&cur);
-  for (size_t i = 0; i < g_ws.size();) {
-    WsSlot* w = g_ws[i];
-    if (w->busy) { i++; continue; }
-    (void)hipSetDevice(w->device);
-    if (w->used) {   // (no event = released in single-stream mode; its stream handle may be gone: wait for the device)
-      hipError_t e = w->ev_valid ? hipEventSynchronize(w->done) : hipDeviceSynchronize();
-      if (e != hipSuccess) (void)hipGetLastError();
-    }
-    ws_free_slot(w);
-    g_ws[i] = g_ws.back();
-    g_ws.pop_back();
-  }
-  if (cur >= 0) (void)hipSetDevice(cur);
-  return RONK_OK;
-}
-// the one-launch scans keep host state per call (which look-back array is clean): not for a capturing stream
-static bool stream_is_capturing(hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return st != hipStreamCaptureStatusNone;
-}
 static void build_horner_tab2(u64 p, u64 z, u64 scale, HornerTab2* t) {
   u64 x = 1 % p;
   for (int i = 0; i < 256; i++) { t->zt[i] = x; x = h_mulmod(x, z, p); }
@@ -343,7 +134,7 @@ extern "C" int ronk_poly_eval_dev(uint64_t p, const uint64_t* d_c, size_t d, uin
     make_horner_tab2(p, x % p, 1, &tab2);
     WsLease ws;
     RCHK(ws.acquire(nch * 8, s));
-    if (nch <= LB_MAX && !g_no_onepass_scans && !stream_is_capturing(s)) {   // one launch (scan_kernels.h)
+    if (nch <= LB_MAX && !g_no_onepass_scans && !stream_capturing(s)) {   // one launch (scan_kernels.h)
       u64 *cur, *next;
       ws.lb_arrays(&cur, &next);
       FIELD_DISPATCH(f, { hipLaunchKernelGGL((eval_onepass_kernel<decltype(ops)>), dim3((u32)nch), dim3(256), 0, s, ops, d_c, d,
@@ -373,12 +164,12 @@ extern "C" int ronk_poly_eval(uint64_t p, const uint64_t* c, size_t d, uint64_t 
   FieldCtx f;
   RCHK(make_field(p, &f));
   if (d == 0) { *out = 0; return RONK_OK; }
-  DevBuf dc, dres;
-  RCHK(dc.alloc(d * 8)); RCHK(dres.alloc(8));
-  HIPCHK(hipMemcpy(dc.p, c, d * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_poly_eval_dev(p, dc.u(), d, x, dres.u(), 0));
-  HIPCHK(hipMemcpy(out, dres.p, 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64* dc = hc.in(c, d);
+  u64* dres = hc.out(1);
+  RCHK(hc.rc);
+  RCHK(ronk_poly_eval_dev(p, dc, d, x, dres, 0));
+  return hc.get(out, dres, 8);
 }
 
 // poly / (b0 + b1 x), b1 != 0: the kzg::open shape (src/kzg/setup.rs:63-78).  d_quot: d coefficients (the top one
@@ -412,7 +203,7 @@ extern "C" int ronk_poly_div_linear_dev(uint64_t p, const uint64_t* d_c, size_t 
     const size_t nch1 = (d + (size_t)LINDIV1_NL * pl1 - 1) / ((size_t)LINDIV1_NL * pl1);
     const bool overlap1 = d_quot < d_c + d && d_c < d_quot + d;
     if (g_lindiv_one && z != 0 && (direct || !LINDIV1_DIRECT) && nch1 <= g_lindiv_one_maxch && !overlap1 && !g_no_onepass_scans &&
-        !stream_is_capturing(s)) {
+        !stream_capturing(s)) {
       LinDiv1Tab tab1;
       make_lindiv1_tab(p, z, b1inv, pl1, &tab1);
       WsLease ws;
@@ -446,7 +237,7 @@ extern "C" int ronk_poly_div_linear_dev(uint64_t p, const uint64_t* d_c, size_t 
     // one launch (scan_kernels.h); not for a quotient written over the dividend: a workgroup whose wait runs out recomputes
     // the chunk sums above it from the coefficients, which other workgroups may have overwritten by then
     const bool overlap = d_quot < d_c + d && d_c < d_quot + d;
-    if (g_onepass_div && !overlap && nch <= LB_DIV_MAX && !g_no_onepass_scans && !stream_is_capturing(s)) {
+    if (g_onepass_div && !overlap && nch <= LB_DIV_MAX && !g_no_onepass_scans && !stream_capturing(s)) {
       u64 *cur, *next;
       ws.lb_arrays(&cur, &next);
       FIELD_DISPATCH(f, { hipLaunchKernelGGL((lindiv_onepass_kernel<decltype(ops)>), dim3((u32)nch), dim3(256), 0, s, ops, d_c, d,
@@ -475,6 +266,14 @@ extern "C" int ronk_poly_div_linear_dev(uint64_t p, const uint64_t* d_c, size_t 
   return RONK_OK;
 }
 
+// the distinct prime factors of n (lagrange_check_kernel tests the nodes' order against them)
+static LagPrimes lag_primes(size_t n) {
+  LagPrimes pr;
+  pr.count = 0;
+  for (size_t q = 2; q * q <= n; q++) if (n % q == 0) { pr.q[pr.count++] = q; while (n % q == 0) n /= q; }
+  if (n > 1) pr.q[pr.count++] = n;
+  return pr;
+}
 // Polynomial::<Lagrange<F>,F,D>::evaluate (polynomial/mod.rs:382-415), device resident.  d_status (may be NULL): set
 // non-zero when two nodes coincide (the reference's F::ONE.div(ZERO) -> unwrap on None = RONK_ERR_ZERO_INVERSE).
 extern "C" int ronk_lagrange_eval_dev(uint64_t p, const uint64_t* d_c, const uint64_t* d_nodes, size_t n, uint64_t x,
@@ -489,10 +288,7 @@ extern "C" int ronk_lagrange_eval_dev(uint64_t p, const uint64_t* d_c, const uin
     // O(n) form for nodes = consecutive powers of an order-n element (what Lagrange::new builds); *d_status bit 2 = the
     // nodes are something else (the general O(n^2) formula is limited to n <= 2^16)
     if (!d_status || n > ((size_t)1 << 32)) return RONK_ERR_UNSUPPORTED;
-    LagPrimes pr;
-    pr.count = 0;
-    { size_t m = n; for (size_t q = 2; q * q <= m; q++) if (m % q == 0) { pr.q[pr.count++] = q; while (m % q == 0) m /= q; }
-      if (m > 1) pr.q[pr.count++] = m; }
+    const LagPrimes pr = lag_primes(n);
     const u32 gb = grid_for(n);
     WsLease ws;
     RCHK(ws.acquire((size_t)gb * 8 + 64, s));
@@ -519,10 +315,7 @@ extern "C" int ronk_lagrange_eval_dev(uint64_t p, const uint64_t* d_c, const uin
     sel = (int*)(ws.u() + 2 * (size_t)blocks + 1);
     u64* fs = ws.u() + 2 * (size_t)blocks + 2;
     HIPCHK(hipMemsetAsync(sel, 0, 4, s));
-    LagPrimes pr;
-    pr.count = 0;
-    { size_t m = n; for (size_t q = 2; q * q <= m; q++) if (m % q == 0) { pr.q[pr.count++] = q; while (m % q == 0) m /= q; }
-      if (m > 1) pr.q[pr.count++] = m; }
+    const LagPrimes pr = lag_primes(n);
     FIELD_DISPATCH(f, {
       hipLaunchKernelGGL((lagrange_check_kernel<decltype(ops)>), dim3(blocks), dim3(256), 0, s, ops, d_nodes, n, pr, sel);
       hipLaunchKernelGGL((lagrange_fast_terms_kernel<decltype(ops)>), dim3(blocks), dim3(256), 0, s, ops, d_c, d_nodes, n, x % p, fs);
@@ -542,18 +335,17 @@ extern "C" int ronk_lagrange_eval_dev(uint64_t p, const uint64_t* d_c, const uin
 extern "C" int ronk_lagrange_eval(uint64_t p, const uint64_t* c, const uint64_t* nodes, size_t n, uint64_t x, uint64_t* out) {
   if (!c || !nodes || !out || n == 0) return RONK_ERR_INVALID;
   RCHK(need_device());
-  DevBuf dc, dn, dres, dflag;
-  RCHK(dc.alloc(n * 8)); RCHK(dn.alloc(n * 8)); RCHK(dres.alloc(8)); RCHK(dflag.alloc(4));
-  HIPCHK(hipMemcpy(dc.p, c, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dn.p, nodes, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dflag.p, 0, 4));
-  RCHK(ronk_lagrange_eval_dev(p, dc.u(), dn.u(), n, x, dres.u(), (int*)dflag.p, 0));
+  HostCall hc;
+  const u64 *dc = hc.in(c, n), *dn = hc.in(nodes, n);
+  u64* dres = hc.out(1);
+  int* dflag = hc.status();
+  RCHK(hc.rc);
+  RCHK(ronk_lagrange_eval_dev(p, dc, dn, n, x, dres, dflag, 0));
   int hflag = 0;
-  HIPCHK(hipMemcpy(&hflag, dflag.p, 4, hipMemcpyDeviceToHost));
+  RCHK(hc.get(&hflag, dflag, 4));
   if (hflag & 4) return RONK_ERR_UNSUPPORTED;   // more than 2^16 nodes that are not the powers of an order-n element
   if (hflag) return RONK_ERR_ZERO_INVERSE;      // coincident nodes: F::ONE.div(ZERO) -> unwrap on None
-  HIPCHK(hipMemcpy(out, dres.p, 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  return hc.get(out, dres, 8);
 }
 
 // ------------------------------------------------------------------------------ fast general division (any NTT-friendly prime)
@@ -646,38 +438,35 @@ int newton_ladder_dev(const FieldCtx& fld, u64 G, const u64* f, size_t Lp, u64* 
 // a: d coefficients with degree n (a[n] != 0), b: degree m (b[m] != 0), n >= m.  d_quot / d_rem: d coefficients each.
 // full_status: the device word that receives RONK_ERR_INVALID when a[n] or b[m] turns out to be ZERO (nullptr: the caller has
 // looked at the operands itself)
-static int newton_divrem_dev(const FieldCtx& fld, u64 G, const u64* d_a, size_t d, size_t n, const u64* d_b, size_t d2, size_t m,
+static int newton_divrem_dev(const FieldCtx& fld, u64 G, const u64* d_a, size_t d, size_t n, const u64* d_b, size_t m,
                              int* full_status, u64* d_quot, u64* d_rem, hipStream_t s) {
   const u64 P = fld.p;
   const size_t L = n - m + 1;                       // coefficients of the true quotient
   size_t Lp = 1; while (Lp < L) Lp <<= 1;           // Newton runs to a power-of-two precision
   // temporaries from the event-guarded workspace pool (one lease, carved up): nothing is allocated, freed or waited for
   // per call, so the entry point stays asynchronous on `s`
-  struct Span { u64* p; u64* u() const { return p; } };
   const size_t n_ar = (L > d ? L : d) + 1, n_qr = 2 * L, n_prod = L + m + 1;
   WsLease ws;
   RCHK(ws.acquire((Lp + 2 * Lp + 4 * Lp + Lp + 2 * Lp + n_ar + n_qr + n_prod) * 8, s));
-  u64* cur = ws.u();
-  auto take = [&](size_t cnt) { Span sp{cur}; cur += cnt; return sp; };
-  const Span f = take(Lp), g = take(2 * Lp), e = take(4 * Lp), h = take(Lp), t1 = take(2 * Lp), ar = take(n_ar), qr = take(n_qr),
-             prod = take(n_prod);
+  Carve c{ws.u()};
+  u64 *f = c.take(Lp), *g = c.take(2 * Lp), *e = c.take(4 * Lp), *h = c.take(Lp), *t1 = c.take(2 * Lp), *ar = c.take(n_ar),
+      *qr = c.take(n_qr), *prod = c.take(n_prod);
   // f = rev(b) mod x^Lp: f[i] = b[m - i] for i <= min(m, Lp - 1), ZERO above
   const size_t flen = (m + 1 < Lp) ? m + 1 : Lp;
-  if (flen < Lp) hipLaunchKernelGGL(dv_copy_kernel, dim3(grid_for(Lp - flen)), dim3(256), 0, s, (const u64*)nullptr, (size_t)0, f.u() + flen, Lp - flen);
-  hipLaunchKernelGGL(dv_reverse_kernel, dim3(grid_for(flen)), dim3(256), 0, s, d_b, m, f.u(), flen);
+  if (flen < Lp) hipLaunchKernelGGL(dv_copy_kernel, dim3(grid_for(Lp - flen)), dim3(256), 0, s, (const u64*)nullptr, (size_t)0, f + flen, Lp - flen);
+  hipLaunchKernelGGL(dv_reverse_kernel, dim3(grid_for(flen)), dim3(256), 0, s, d_b, m, f, flen);
   // g = 1 / f[0] = 1 / lead(b)   (precision 1)
-  FIELD_DISPATCH(fld, { hipLaunchKernelGGL((dv_fill_inv_kernel<decltype(ops)>), dim3(grid_for(2 * Lp)), dim3(256), 0, s, ops, g.u(), 2 * Lp,
+  FIELD_DISPATCH(fld, { hipLaunchKernelGGL((dv_fill_inv_kernel<decltype(ops)>), dim3(grid_for(2 * Lp)), dim3(256), 0, s, ops, g, 2 * Lp,
                                           d_b + m, d_a + n, full_status); });
-  RCHK(newton_ladder_dev(fld, G, f.u(), Lp, g.u(), e.u(), h.u(), t1.u(), s));
+  RCHK(newton_ladder_dev(fld, G, f, Lp, g, e, h, t1, s));
   // qrev = (rev(a)[0:L] * g[0:L])[0:L]
-  hipLaunchKernelGGL(dv_reverse_kernel, dim3(grid_for(L)), dim3(256), 0, s, d_a, n, ar.u(), L);
-  RCHK(ronk_poly_mul_dev(P, G, ar.u(), L, g.u(), L, qr.u(), s));
-  const size_t t = 0;                               // d2 == m + 1: every quotient coefficient is produced
-  (void)d2;
-  hipLaunchKernelGGL(dv_quot_kernel, dim3(grid_for(d)), dim3(256), 0, s, qr.u(), L, t, d_quot, d);
+  hipLaunchKernelGGL(dv_reverse_kernel, dim3(grid_for(L)), dim3(256), 0, s, d_a, n, ar, L);
+  RCHK(ronk_poly_mul_dev(P, G, ar, L, g, L, qr, s));
+  // (the divisor is full length, m + 1 coefficients: every quotient coefficient is produced, none cleared from below)
+  hipLaunchKernelGGL(dv_quot_kernel, dim3(grid_for(d)), dim3(256), 0, s, (const u64*)qr, L, (size_t)0, d_quot, d);
   // rem = a - quot[0:L] * b[0:m+1]
-  RCHK(ronk_poly_mul_dev(P, G, d_quot, L, d_b, m + 1, prod.u(), s));
-  FIELD_DISPATCH(fld, { hipLaunchKernelGGL((dv_rem_kernel<decltype(ops)>), dim3(grid_for(d)), dim3(256), 0, s, ops, d_a, prod.u(), L + m, d_rem, d); });
+  RCHK(ronk_poly_mul_dev(P, G, d_quot, L, d_b, m + 1, prod, s));
+  FIELD_DISPATCH(fld, { hipLaunchKernelGGL((dv_rem_kernel<decltype(ops)>), dim3(grid_for(d)), dim3(256), 0, s, ops, d_a, (const u64*)prod, L + m, d_rem, d); });
   HIPCHK(hipGetLastError());
   return RONK_OK;                                   // the lease's destructor leaves an event behind the last kernel
 }
@@ -698,6 +487,17 @@ __global__ void dv_lead_kernel(const u64* __restrict__ b, unsigned long long* __
   out[2] = out[1] ? b[out[1] - 1] : 0;
 }
 
+// the one-workgroup long division that follows the reference's loop (d_rem may be d_a: the kernel copies the dividend, and clears
+// the status, itself)
+static int longdiv_launch(const FieldCtx& f, const u64* d_a, size_t d, const u64* d_b, size_t d2, u64* d_quot, u64* d_rem, int* d_status,
+                          hipStream_t s) {
+  const u32 T = d2 >= 1024 ? 1024 : d2 > 256 ? 512 : 256;
+  FIELD_DISPATCH(f, { hipLaunchKernelGGL((poly_divrem_kernel<decltype(ops)>), dim3(1), dim3(T), 0, s, ops, d_a, d_rem, d, d_b, d2,
+                                        d_quot, d_status); });
+  HIPCHK(hipGetLastError());
+  return RONK_OK;
+}
+
 // quotient_and_remainder on device-resident operands.  d_quot / d_rem receive d coefficients each (d_rem may alias d_a);
 // *d_status (device int, required) receives 0 or the RONK_ERR_* code of the reference's panic.
 // Any prime, any divisor: the long-division kernel that follows the reference's loop, asynchronous on `stream`.
@@ -714,14 +514,13 @@ extern "C" int ronk_poly_divrem_dev(uint64_t p, const uint64_t* d_a, size_t d, c
   hipStream_t s = (hipStream_t)stream;
   u64 gz = 0;
   if (d >= d2 && d2 >= 64 && d - d2 + 1 >= 2048 && newton_field(f, d, &gz)) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    const bool cap = stream_capturing(s);
     // A capturing stream cannot be synchronised for the degree probe.  Where the one-workgroup long division is still a
     // matter of milliseconds it is captured instead; beyond that (d2 * (d - d2 + 1) field operations on ONE workgroup: seconds to
     // minutes) the call is refused rather than silently captured as a kernel nobody can afford -- ronk_poly_divrem_full_dev is
     // the capturable O(n log n) form.
-    if (cap != hipStreamCaptureStatusNone && (double)d2 * (double)(d - d2 + 1) > 1.0e9) return RONK_ERR_UNSUPPORTED;
-    if (cap == hipStreamCaptureStatusNone) {
+    if (cap && (double)d2 * (double)(d - d2 + 1) > 1.0e9) return RONK_ERR_UNSUPPORTED;
+    if (!cap) {
       unsigned long long probe[3] = {0, 0, 0};
       {
         WsLease ws;
@@ -739,15 +538,11 @@ extern "C" int ronk_poly_divrem_dev(uint64_t p, const uint64_t* d_a, size_t d, c
       // the long-division kernel), a quotient long enough for the O(n log n) form to win
       if (n > 0 && m == d2 && n >= m && (n - m + 1) >= 2048 && m >= 64) {
         HIPCHK(hipMemsetAsync(d_status, 0, 4, s));
-        return newton_divrem_dev(f, gz, d_a, d, n - 1, d_b, d2, m - 1, nullptr, d_quot, d_rem, s);
+        return newton_divrem_dev(f, gz, d_a, d, n - 1, d_b, m - 1, nullptr, d_quot, d_rem, s);
       }
     }
   }
-  const u32 T = d2 >= 1024 ? 1024 : d2 > 256 ? 512 : 256;
-  FIELD_DISPATCH(f, { hipLaunchKernelGGL((poly_divrem_kernel<decltype(ops)>), dim3(1), dim3(T), 0, s, ops, d_a, d_rem, d, d_b, d2,
-                                        d_quot, d_status); });   // (copies the dividend and clears the status itself)
-  HIPCHK(hipGetLastError());
-  return RONK_OK;
+  return longdiv_launch(f, d_a, d, d_b, d2, d_quot, d_rem, d_status, s);
 }
 
 // quotient_and_remainder for FULL-LENGTH operands (a[d - 1] != 0, b[d2 - 1] != 0 -- the common case: the caller knows its degrees),
@@ -764,7 +559,7 @@ extern "C" int ronk_poly_divrem_full_dev(uint64_t p, const uint64_t* d_a, size_t
   RCHK(make_field(p, &f));
   u64 gz = 0;
   if (!newton_field(f, d, &gz)) return RONK_ERR_UNSUPPORTED;
-  return newton_divrem_dev(f, gz, d_a, d, d - 1, d_b, d2, d2 - 1, d_status, d_quot, d_rem, (hipStream_t)stream);
+  return newton_divrem_dev(f, gz, d_a, d, d - 1, d_b, d2 - 1, d_status, d_quot, d_rem, (hipStream_t)stream);
 }
 
 extern "C" int ronk_poly_divrem(uint64_t p, const uint64_t* a, size_t d, const uint64_t* b, size_t d2, uint64_t* quot,
@@ -774,15 +569,15 @@ extern "C" int ronk_poly_divrem(uint64_t p, const uint64_t* a, size_t d, const u
   FieldCtx f;
   RCHK(make_field(p, &f));
   // kzg::open shape (src/kzg/setup.rs:63-78): a linear divisor b0 + b1*x with b1 != 0 -> Horner scan
+  HostCall hc;
   if (d2 == 2 && b[1] % p != 0 && d <= HORNER_MAX) {
-    DevBuf dc, dqq, dr;
-    RCHK(dc.alloc(d * 8)); RCHK(dqq.alloc(d * 8)); RCHK(dr.alloc(8));
-    HIPCHK(hipMemcpy(dc.p, a, d * 8, hipMemcpyHostToDevice));
-    RCHK(ronk_poly_div_linear_dev(p, dc.u(), d, b[0], b[1], dqq.u(), dr.u(), 0));
-    HIPCHK(hipMemcpy(quot, dqq.p, d * 8, hipMemcpyDeviceToHost));
+    const u64* dc = hc.in(a, d);
+    u64 *dq = hc.out(d), *dr = hc.out(1);
+    RCHK(hc.rc);
+    RCHK(ronk_poly_div_linear_dev(p, dc, d, b[0], b[1], dq, dr, 0));
+    RCHK(hc.get(quot, dq, d * 8));
     memset(rem, 0, d * 8);
-    HIPCHK(hipMemcpy(rem, dr.p, 8, hipMemcpyDeviceToHost));
-    return RONK_OK;
+    return hc.get(rem, dr, 8);
   }
   // general divisor over Goldilocks, large enough for the O(n log n) form to win: Newton inversion on the NTT path.
   // Zero operands, short dividends and the reference's panics keep going through the long-division kernel below,
@@ -793,32 +588,25 @@ extern "C" int ronk_poly_divrem(uint64_t p, const uint64_t* a, size_t d, const u
     while (n > 0 && a[n - 1] % p == 0) n--;        // n = degree + 1 of the dividend (0: zero polynomial)
     while (m > 0 && b[m - 1] % p == 0) m--;
     if (n > 0 && m == d2 && n >= m && (n - m + 1) >= 2048 && m >= 64) {
-      const size_t dn = n - 1, dm = m - 1;
-      DevBuf da, db2, dq2, dr2;
-      RCHK(da.alloc(d * 8)); RCHK(db2.alloc(d2 * 8)); RCHK(dq2.alloc(d * 8)); RCHK(dr2.alloc(d * 8));
-      HIPCHK(hipMemcpy(da.p, a, d * 8, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(db2.p, b, d2 * 8, hipMemcpyHostToDevice));
-      RCHK(newton_divrem_dev(f, gz, da.u(), d, dn, db2.u(), d2, dm, nullptr, dq2.u(), dr2.u(), 0));
-      HIPCHK(hipMemcpy(quot, dq2.p, d * 8, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(rem, dr2.p, d * 8, hipMemcpyDeviceToHost));
-      return RONK_OK;
+      const u64 *da = hc.in(a, d), *db = hc.in(b, d2);
+      u64 *dq = hc.out(d), *dr = hc.out(d);
+      RCHK(hc.rc);
+      RCHK(newton_divrem_dev(f, gz, da, d, n - 1, db, m - 1, nullptr, dq, dr, 0));
+      RCHK(hc.get(quot, dq, d * 8));
+      return hc.get(rem, dr, d * 8);
     }
   }
-  DevBuf drem, db, dq, dst;
-  RCHK(drem.alloc(d * 8)); RCHK(db.alloc(d2 * 8)); RCHK(dq.alloc(d * 8)); RCHK(dst.alloc(4));
-  HIPCHK(hipMemcpy(drem.p, a, d * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(db.p, b, d2 * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dst.p, 0, 4));
-  const u32 T = d2 >= 1024 ? 1024 : d2 > 256 ? 512 : 256;
-  FIELD_DISPATCH(f, { hipLaunchKernelGGL((poly_divrem_kernel<decltype(ops)>), dim3(1), dim3(T), 0, 0, ops, (const u64*)drem.u(), drem.u(), d,
-                                        db.u(), d2, dq.u(), (int*)dst.p); });
-  HIPCHK(hipGetLastError());
+  u64* drem = hc.in(a, d);   // the dividend, divided in place
+  const u64* db = hc.in(b, d2);
+  u64* dq = hc.out(d);
+  int* dst = hc.status();
+  RCHK(hc.rc);
+  RCHK(longdiv_launch(f, drem, d, db, d2, dq, drem, dst, 0));
   int status = 0;
-  HIPCHK(hipMemcpy(&status, dst.p, 4, hipMemcpyDeviceToHost));
+  RCHK(hc.get(&status, dst, 4));
   if (status) return status;
-  HIPCHK(hipMemcpy(quot, dq.p, d * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(rem, drem.p, d * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  RCHK(hc.get(quot, dq, d * 8));
+  return hc.get(rem, drem, d * 8);
 }
 
 // Message::encode::<N> (codes/reed_solomon.rs:42-52) == nodes + size-N DFT of the zero-padded message
@@ -839,28 +627,25 @@ extern "C" int ronk_rs_encode(uint64_t p, uint64_t g, const uint64_t* msg, size_
 // Asynchronous on `s`: the temporaries are one lease of the event-guarded workspace pool.
 static int rs_decode_fast_dev(const u64* d_xs, const u64* d_ys, size_t k, u64* d_out, int* sel, hipStream_t s) {
   const u64 P = RONK_GOLDILOCKS_P, G = RONK_GOLDILOCKS_G;
-  struct Span { u64* p; u64* u() const { return p; } };
   WsLease ws;
   RCHK(ws.acquire(((k + 1) + k + (2 * k - 1) + (3 * k - 2) + (k + 1) + k + 2 * k + 1025) * 8, s));
-  u64* cur = ws.u();
-  auto take = [&](size_t cnt) { Span sp{cur}; cur += cnt; return sp; };
-  const Span B = take(k + 1), arev = take(k), b = take(2 * k - 1), conv = take(3 * k - 2), M = take(k + 1), srev = take(k),
-             conv2 = take(2 * k), tot = take(1025);
+  Carve c{ws.u()};
+  u64 *B = c.take(k + 1), *arev = c.take(k), *b = c.take(2 * k - 1), *conv = c.take(3 * k - 2), *M = c.take(k + 1), *srev = c.take(k),
+      *conv2 = c.take(2 * k), *tot = c.take(1025);
   const size_t m = k + 1;
   const u32 nb = (u32)((m + 256 * RSF_PER - 1) / (256 * RSF_PER));
   hipLaunchKernelGGL(rsf_check_kernel, dim3((u32)((k + 255) / 256)), dim3(256), 0, s, d_xs, k, sel);
-  hipLaunchKernelGGL(rsf_factors_kernel, dim3(grid_for(m)), dim3(256), 0, s, d_xs, k, B.u());
-  hipLaunchKernelGGL(rsf_scan_totals_kernel, dim3(nb), dim3(256), 0, s, (const u64*)B.u(), m, tot.u());
-  hipLaunchKernelGGL(rsf_scan_mid_kernel, dim3(1), dim3(1024), 0, s, tot.u(), nb);
-  hipLaunchKernelGGL(rsf_scan_apply_kernel, dim3(nb), dim3(256), 0, s, B.u(), m, (const u64*)tot.u());
-  hipLaunchKernelGGL(rsf_prepare_kernel, dim3(grid_for(2 * k - 1)), dim3(256), 0, s, d_xs, d_ys, (const u64*)B.u(), k, arev.u(), b.u(),
-                     M.u());
+  hipLaunchKernelGGL(rsf_factors_kernel, dim3(grid_for(m)), dim3(256), 0, s, d_xs, k, B);
+  hipLaunchKernelGGL(rsf_scan_totals_kernel, dim3(nb), dim3(256), 0, s, (const u64*)B, m, tot);
+  hipLaunchKernelGGL(rsf_scan_mid_kernel, dim3(1), dim3(1024), 0, s, tot, nb);
+  hipLaunchKernelGGL(rsf_scan_apply_kernel, dim3(nb), dim3(256), 0, s, B, m, (const u64*)tot);
+  hipLaunchKernelGGL(rsf_prepare_kernel, dim3(grid_for(2 * k - 1)), dim3(256), 0, s, d_xs, d_ys, (const u64*)B, k, arev, b, M);
   HIPCHK(hipGetLastError());
-  RCHK(ronk_poly_mul_dev(P, G, arev.u(), k, b.u(), 2 * k - 1, conv.u(), s));
-  hipLaunchKernelGGL(rsf_unchirp_kernel, dim3(grid_for(k)), dim3(256), 0, s, d_xs, (const u64*)conv.u(), k, srev.u());
+  RCHK(ronk_poly_mul_dev(P, G, arev, k, b, 2 * k - 1, conv, s));
+  hipLaunchKernelGGL(rsf_unchirp_kernel, dim3(grid_for(k)), dim3(256), 0, s, d_xs, (const u64*)conv, k, srev);
   HIPCHK(hipGetLastError());
-  RCHK(ronk_poly_mul_dev(P, G, srev.u(), k, M.u(), k + 1, conv2.u(), s));
-  hipLaunchKernelGGL(rsf_extract_kernel, dim3(grid_for(k)), dim3(256), 0, s, (const u64*)conv2.u(), k, (const int*)sel, d_out);
+  RCHK(ronk_poly_mul_dev(P, G, srev, k, M, k + 1, conv2, s));
+  hipLaunchKernelGGL(rsf_extract_kernel, dim3(grid_for(k)), dim3(256), 0, s, (const u64*)conv2, k, (const int*)sel, d_out);
   HIPCHK(hipGetLastError());
   return RONK_OK;
 }
@@ -908,24 +693,23 @@ extern "C" int ronk_rs_decode(uint64_t p, const uint64_t* xs, const uint64_t* ys
   RCHK(need_device());
   std::vector<u64> hx(k), hy(k);
   for (size_t i = 0; i < k; i++) { hx[i] = xs[i] % p; hy[i] = ys[i] % p; }
-  DevBuf dx, dy, dout, dflag;
-  RCHK(dx.alloc(k * 8)); RCHK(dy.alloc(k * 8)); RCHK(dout.alloc(k * 8)); RCHK(dflag.alloc(4));
-  HIPCHK(hipMemcpy(dx.p, hx.data(), k * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dy.p, hy.data(), k * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dflag.p, 0, 4));
-  RCHK(ronk_rs_decode_dev(p, dx.u(), dy.u(), k, dout.u(), (int*)dflag.p, 0));
+  HostCall hc;
+  const u64 *dx = hc.in(hx.data(), k), *dy = hc.in(hy.data(), k);
+  u64* dout = hc.out(k);
+  int* dflag = hc.status();
+  RCHK(hc.rc);
+  RCHK(ronk_rs_decode_dev(p, dx, dy, k, dout, dflag, 0));
   int hflag = 0;
-  HIPCHK(hipMemcpy(&hflag, dflag.p, 4, hipMemcpyDeviceToHost));
+  RCHK(hc.get(&hflag, dflag, 4));
   if (hflag & 4) return RONK_ERR_UNSUPPORTED;  // more than 2^14 nodes that are not q^j
   if (hflag) return RONK_ERR_ZERO_INVERSE;     // coincident nodes: numerator / ZERO
-  HIPCHK(hipMemcpy(out, dout.p, k * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  return hc.get(out, dout, k * 8);
 }
 
 // kzg::commit (src/kzg/setup.rs:45-60): sum_i points[i] * scalars[i] on y^2 = x^3 + a x + b over F_p[u]/(u^2 - nr).
 // Device resident: d_points = n_points x 5 words (x0, x1, y0, y1, infinity flag; coordinates canonical), d_scalars = n
-// words, d_out = 5 words.  *d_status (device int, required; the caller zeroes it): bit 0 = a point is not on the curve
-// (AffinePoint::new's panic), bit 1 = a division by zero inside the group law.  With ronk_poly_div_linear_dev the whole of
+// words, d_out = 5 words.  *d_status (device int, required; the caller zeroes it): bit 1 = a point is not on the curve
+// (AffinePoint::new's panic), bit 0 = a division by zero inside the group law (curve_kernels.h CURVE_ERR_*).  With ronk_poly_div_linear_dev the whole of
 // kzg::open (src/kzg/setup.rs:63-78: quotient, then commit) stays on the device.
 extern "C" int ronk_curve_msm_dev(const ronk_curve* cv, const uint64_t* d_points, size_t n_points, const uint64_t* d_scalars,
                                   size_t n, uint64_t* d_out, int* d_status, void* stream) {
@@ -966,16 +750,15 @@ extern "C" int ronk_curve_msm(const ronk_curve* cv, const uint64_t* points, size
     hp[5 * i + 4] = points[5 * i + 4] ? 1 : 0;
     hs[i] = scalars[i];
   }
-  DevBuf dp, ds, dout, dflag;
-  RCHK(dp.alloc(5 * n * 8)); RCHK(ds.alloc(n * 8)); RCHK(dout.alloc(5 * 8)); RCHK(dflag.alloc(4));
-  HIPCHK(hipMemcpy(dp.p, hp.data(), 5 * n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds.p, hs.data(), n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dflag.p, 0, 4));
-  RCHK(ronk_curve_msm_dev(cv, dp.u(), n, ds.u(), n, dout.u(), (int*)dflag.p, 0));
+  HostCall hc;
+  const u64 *dp = hc.in(hp.data(), 5 * n), *ds = hc.in(hs.data(), n);
+  u64* dout = hc.out(5);
+  int* dflag = hc.status();
+  RCHK(hc.rc);
+  RCHK(ronk_curve_msm_dev(cv, dp, n, ds, n, dout, dflag, 0));
   int hflag = 0;
-  HIPCHK(hipMemcpy(&hflag, dflag.p, 4, hipMemcpyDeviceToHost));
+  RCHK(hc.get(&hflag, dflag, 4));
   if (hflag & CURVE_ERR_NOT_ON_CURVE) return RONK_ERR_NOT_ON_CURVE;   // AffinePoint::new: "Point is not on curve"
   if (hflag & CURVE_ERR_INVERSE) return RONK_ERR_ZERO_INVERSE;        // Div: expect("invalid inverse")
-  HIPCHK(hipMemcpy(out, dout.p, 5 * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  return hc.get(out, dout, 5 * 8);
 }

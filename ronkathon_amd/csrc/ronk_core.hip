@@ -130,13 +130,12 @@ template <int OP>
 static int vec_binary_host(u64 p, const u64* a, size_t n, const u64* b, size_t nb, u64* out) {
   if (!a || !b || !out) return RONK_ERR_INVALID;
   RCHK(need_device());
-  DevBuf da, db;
-  RCHK(da.alloc(n * 8)); RCHK(db.alloc(nb * 8));
-  HIPCHK(hipMemcpy(da.p, a, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(db.p, b, nb * 8, hipMemcpyHostToDevice));
-  RCHK((vec_binary_dev<OP>(p, da.u(), db.u(), da.u(), n, nb, 0)));
-  HIPCHK(hipMemcpy(out, da.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  u64* da = hc.in(a, n);
+  const u64* db = hc.in(b, nb);
+  RCHK(hc.rc);
+  RCHK((vec_binary_dev<OP>(p, da, db, da, n, nb, 0)));
+  return hc.get(out, da, n * 8);
 }
 extern "C" int ronk_vec_add(uint64_t p, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
   return vec_binary_host<VEC_ADD>(p, a, n, b, n, out);
@@ -188,45 +187,41 @@ extern "C" int ronk_vec_inv_dev(uint64_t p, const uint64_t* d_a, uint64_t* d_out
   return RONK_OK;
 }
 
+// The host-pointer forms: the field is looked at BEFORE the device copy is made, so a bad p keeps its code whatever n is.
+static int field_check(u64 p) { FieldCtx f; return make_field(p, &f); }
 extern "C" int ronk_vec_neg(uint64_t p, const uint64_t* a, uint64_t* out, size_t n) {
   if (!a || !out) return RONK_ERR_INVALID;
   RCHK(need_device());
-  FieldCtx f;
-  RCHK(make_field(p, &f));
-  DevBuf da;
-  RCHK(da.alloc(n * 8));
-  HIPCHK(hipMemcpy(da.p, a, n * 8, hipMemcpyHostToDevice));
-  if (n) FIELD_DISPATCH(f, { hipLaunchKernelGGL((vec_neg_kernel<decltype(ops)>), dim3(grid_for(n)), dim3(256), 0, 0, ops,
-                                               da.u(), da.u(), n); });
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(out, da.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
-}
-static int vec_pow_host(u64 p, const u64* a, u64 e, u64* out, size_t n, bool is_inverse) {
-  if (!a || !out) return RONK_ERR_INVALID;
-  RCHK(need_device());
-  FieldCtx f;
-  RCHK(make_field(p, &f));
-  DevBuf da, dflag;
-  RCHK(da.alloc(n * 8)); RCHK(dflag.alloc(4));
-  HIPCHK(hipMemcpy(da.p, a, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dflag.p, 0, 4));
-  int* flag = is_inverse ? (int*)dflag.p : nullptr;
-  if (n) FIELD_DISPATCH(f, { hipLaunchKernelGGL((vec_pow_kernel<decltype(ops)>), dim3(grid_for(n)), dim3(256), 0, 0, ops,
-                                               da.u(), e, da.u(), n, flag); });
-  HIPCHK(hipGetLastError());
-  int hflag = 0;
-  HIPCHK(hipMemcpy(&hflag, dflag.p, 4, hipMemcpyDeviceToHost));
-  if (hflag) return RONK_ERR_ZERO_INVERSE;
-  HIPCHK(hipMemcpy(out, da.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  RCHK(field_check(p));
+  HostCall hc;
+  u64* da = hc.in(a, n);
+  RCHK(hc.rc);
+  RCHK(ronk_vec_neg_dev(p, da, da, n, nullptr));
+  return hc.get(out, da, n * 8);
 }
 extern "C" int ronk_vec_pow(uint64_t p, const uint64_t* a, uint64_t e, uint64_t* out, size_t n) {
-  return vec_pow_host(p, a, e, out, n, false);
+  if (!a || !out) return RONK_ERR_INVALID;
+  RCHK(need_device());
+  RCHK(field_check(p));
+  HostCall hc;
+  u64* da = hc.in(a, n);
+  RCHK(hc.rc);
+  RCHK(ronk_vec_pow_dev(p, da, e, da, n, nullptr));
+  return hc.get(out, da, n * 8);
 }
 extern "C" int ronk_vec_inv(uint64_t p, const uint64_t* a, uint64_t* out, size_t n) {
-  if (p < 2) return RONK_ERR_INVALID;
-  return vec_pow_host(p, a, p - 2, out, n, true);
+  if (!a || !out || p < 2) return RONK_ERR_INVALID;
+  RCHK(need_device());
+  RCHK(field_check(p));
+  HostCall hc;
+  u64* da = hc.in(a, n);
+  int* dflag = hc.status();
+  RCHK(hc.rc);
+  RCHK(ronk_vec_inv_dev(p, da, da, n, dflag, nullptr));
+  int hflag = 0;
+  RCHK(hc.get(&hflag, dflag, 4));
+  if (hflag) return RONK_ERR_ZERO_INVERSE;
+  return hc.get(out, da, n * 8);
 }
 
 // FieldExt (src/algebra/field/mod.rs:79-84; prime/mod.rs:142-226) over arrays.  The constants of the prime -- p - 1 = q 2^s and
@@ -266,27 +261,25 @@ extern "C" int ronk_vec_sqrt_dev(uint64_t p, const uint64_t* d_a, uint64_t* d_r0
 extern "C" int ronk_vec_euler(uint64_t p, const uint64_t* a, uint64_t* out, size_t n) {
   if (!a || !out) return RONK_ERR_INVALID;
   RCHK(need_device());
-  DevBuf da;
-  RCHK(da.alloc(n * 8));
-  HIPCHK(hipMemcpy(da.p, a, n * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_vec_euler_dev(p, da.u(), da.u(), n, nullptr));
-  HIPCHK(hipMemcpy(out, da.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  u64* da = hc.in(a, n);
+  RCHK(hc.rc);
+  RCHK(ronk_vec_euler_dev(p, da, da, n, nullptr));
+  return hc.get(out, da, n * 8);
 }
 extern "C" int ronk_vec_sqrt(uint64_t p, const uint64_t* a, uint64_t* r0, uint64_t* r1, size_t n) {
   if (!a || !r0 || !r1) return RONK_ERR_INVALID;
   RCHK(need_device());
-  DevBuf da, db, dflag;
-  RCHK(da.alloc(n * 8)); RCHK(db.alloc(n * 8)); RCHK(dflag.alloc(4));
-  HIPCHK(hipMemcpy(da.p, a, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemset(dflag.p, 0, 4));
-  RCHK(ronk_vec_sqrt_dev(p, da.u(), da.u(), db.u(), n, (int*)dflag.p, nullptr));
+  HostCall hc;
+  u64 *da = hc.in(a, n), *db = hc.out(n);
+  int* dflag = hc.status();
+  RCHK(hc.rc);
+  RCHK(ronk_vec_sqrt_dev(p, da, da, db, n, dflag, nullptr));
   int hflag = 0;
-  HIPCHK(hipMemcpy(&hflag, dflag.p, 4, hipMemcpyDeviceToHost));
+  RCHK(hc.get(&hflag, dflag, 4));
   if (hflag) return RONK_ERR_NOT_RESIDUE;
-  HIPCHK(hipMemcpy(r0, da.p, n * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(r1, db.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  RCHK(hc.get(r0, da, n * 8));
+  return hc.get(r1, db, n * 8);
 }
 
 // ------------------------------------------------------------------------------ device helpers

@@ -3,7 +3,7 @@
 #include <map>
 #include <memory>
 
-#include "runtime.h"
+#include "workspace.h"
 #include "hip_launch.h"
 #include "fr_ntt_kernels.h"
 
@@ -195,12 +195,11 @@ static int fr_transform_host(u32 log2n, bool inverse, const uint64_t* in, uint64
   ronk_fr_plan* raw = nullptr;
   RCHK(ronk_plan_create_bn254(&raw, log2n, 0));
   std::unique_ptr<ronk_fr_plan> pl(raw);
-  const size_t bytes = ((size_t)32) << log2n;
-  DevBuf d;
-  RCHK(d.alloc(bytes));
-  HIPCHK(hipMemcpy(d.p, in, bytes, hipMemcpyHostToDevice));
-  RCHK(fr_transform_dev(pl.get(), inverse, d.u(), d.u(), 1, nullptr));
-  HIPCHK(hipMemcpy(out, d.p, bytes, hipMemcpyDeviceToHost));   // orders behind the null stream's work
+  HostCall hc;
+  u64* d = hc.in(in, (size_t)4 << log2n);
+  RCHK(hc.rc);
+  RCHK(fr_transform_dev(pl.get(), inverse, d, d, 1, nullptr));
+  RCHK(hc.get(out, d, (size_t)32 << log2n));   // orders behind the null stream's work
   HIPCHK(hipDeviceSynchronize());
   return RONK_OK;
 }
@@ -235,11 +234,10 @@ extern "C" int ronk_poly_mul_bn254_dev(const uint64_t* d_a, size_t d, const uint
   ronk_fr_plan* pl = nullptr;
   RCHK(fr_mul_plan(k, &pl));
   // workspace: the two padded operands (one batch of two rows), then two scratch buffers of two rows each
-  void* lease = nullptr;
-  u64* ws = nullptr;
-  RCHK(ws_lease_acquire(6 * n * 32, s, &lease, &ws));
-  struct Release { void* l; ~Release() { ws_lease_release(l); } } release{lease};
-  u64 *ab = ws, *t1 = ws + 8 * n, *t2 = ws + 16 * n;
+  WsLease ws;
+  RCHK(ws.acquire(6 * n * 32, s));
+  Carve c{ws.u()};
+  u64 *ab = c.take(8 * n), *t1 = c.take(8 * n), *t2 = c.take(8 * n);
   hipLaunchKernelGGL(fr_pad_kernel, dim3(grid_for(n)), dim3(256), 0, s, d_a, (u64)d, ab, (u64)n);
   hipLaunchKernelGGL(fr_pad_kernel, dim3(grid_for(n)), dim3(256), 0, s, d_b, (u64)d2, ab + 4 * n, (u64)n);
   HIPCHK(hipGetLastError());
@@ -256,12 +254,12 @@ extern "C" int ronk_poly_mul_bn254(const uint64_t* a, size_t d, const uint64_t* 
   const size_t len = d + d2 - 1;
   if (len < d || len > ((size_t)1 << FR_TWO_ADICITY)) return RONK_ERR_UNSUPPORTED;
   RCHK(need_device());
-  DevBuf da, db, dc;
-  RCHK(da.alloc(d * 32)); RCHK(db.alloc(d2 * 32)); RCHK(dc.alloc(len * 32));
-  HIPCHK(hipMemcpy(da.p, a, d * 32, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(db.p, b, d2 * 32, hipMemcpyHostToDevice));
-  RCHK(ronk_poly_mul_bn254_dev(da.u(), d, db.u(), d2, dc.u(), nullptr));
-  HIPCHK(hipMemcpy(out, dc.p, len * 32, hipMemcpyDeviceToHost));
+  HostCall hc;
+  const u64 *da = hc.in(a, 4 * d), *db = hc.in(b, 4 * d2);
+  u64* dc = hc.out(4 * len);
+  RCHK(hc.rc);
+  RCHK(ronk_poly_mul_bn254_dev(da, d, db, d2, dc, nullptr));
+  RCHK(hc.get(out, dc, len * 32));
   HIPCHK(hipDeviceSynchronize());
   return RONK_OK;
 }

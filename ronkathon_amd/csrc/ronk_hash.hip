@@ -128,12 +128,11 @@ extern "C" int ronk_poseidon_hash(const ronk_poseidon* h, const uint64_t* in, si
   RCHK(need_device());
   std::vector<u64> st(h->width, 0);
   for (size_t i = 0; i < len; i++) st[i] = in[i];
-  DevBuf d;
-  RCHK(d.alloc(h->width * 8));
-  HIPCHK(hipMemcpy(d.p, st.data(), h->width * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_poseidon_permute_dev(h, d.u(), 1, nullptr));
-  HIPCHK(hipMemcpy(out_state, d.p, h->width * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  u64* d = hc.in(st.data(), h->width);
+  RCHK(hc.rc);
+  RCHK(ronk_poseidon_permute_dev(h, d, 1, nullptr));
+  return hc.get(out_state, d, h->width * 8);
 }
 
 extern "C" int ronk_poseidon_sponge_dev(const ronk_poseidon* h, const uint64_t* d_in, size_t n_items, size_t len, size_t item_stride,
@@ -215,12 +214,12 @@ extern "C" int ronk_merkle_commit(const ronk_poseidon* h, const uint64_t* leaves
   if (!h || !tree || (!leaves && leaf_len) || !n_leaves || !digest_len || digest_len > h->rate) return RONK_ERR_INVALID;
   RCHK(need_device());
   const size_t words = ronk_merkle_tree_words(n_leaves, digest_len);
-  DevBuf dl, dt;
-  RCHK(dl.alloc(n_leaves * leaf_len * 8)); RCHK(dt.alloc(words * 8));
-  HIPCHK(hipMemcpy(dl.p, leaves, n_leaves * leaf_len * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_merkle_commit_dev(h, dl.u(), n_leaves, leaf_len, leaf_len, 1, digest_len, dt.u(), nullptr));
-  HIPCHK(hipMemcpy(tree, dt.p, words * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64* dl = hc.in(leaves, n_leaves * leaf_len);   // (NULL for empty leaves)
+  u64* dt = hc.out(words);
+  RCHK(hc.rc);
+  RCHK(ronk_merkle_commit_dev(h, dl, n_leaves, leaf_len, leaf_len, 1, digest_len, dt, nullptr));
+  return hc.get(tree, dt, words * 8);
 }
 
 extern "C" int ronk_merkle_open(const uint64_t* tree, size_t n_leaves, size_t digest_len, const uint64_t* indices, size_t n_idx,
@@ -242,14 +241,11 @@ extern "C" int ronk_merkle_verify(const ronk_poseidon* h, const uint64_t* leaves
   RCHK(need_device());
   if (!n_idx) return RONK_OK;
   const size_t depth = merkle_levels(n_leaves) - 1;
-  DevBuf dl, di, dp, dr, dk;
-  RCHK(dl.alloc(n_idx * leaf_len * 8)); RCHK(di.alloc(n_idx * 8)); RCHK(dp.alloc(n_idx * depth * digest_len * 8));
-  RCHK(dr.alloc(digest_len * 8)); RCHK(dk.alloc(n_idx * 4));
-  if (leaf_len) HIPCHK(hipMemcpy(dl.p, leaves, n_idx * leaf_len * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(di.p, indices, n_idx * 8, hipMemcpyHostToDevice));
-  if (depth) HIPCHK(hipMemcpy(dp.p, paths, n_idx * depth * digest_len * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dr.p, root, digest_len * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_merkle_verify_dev(h, dl.u(), n_idx, leaf_len, leaf_len, 1, di.u(), dp.u(), n_leaves, digest_len, dr.u(), (int*)dk.p, nullptr));
-  HIPCHK(hipMemcpy(ok, dk.p, n_idx * 4, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;   // leaves (empty leaves) and paths (a one-leaf tree) may be NULL
+  const u64 *dl = hc.in(leaves, n_idx * leaf_len), *di = hc.in(indices, n_idx), *dp = hc.in(paths, n_idx * depth * digest_len);
+  const u64* dr = hc.in(root, digest_len);
+  int* dk = (int*)hc.out((n_idx + 1) / 2);   // int ok[n_idx]
+  RCHK(hc.rc);
+  RCHK(ronk_merkle_verify_dev(h, dl, n_idx, leaf_len, leaf_len, 1, di, dp, n_leaves, digest_len, dr, dk, nullptr));
+  return hc.get(ok, dk, n_idx * 4);
 }

@@ -179,11 +179,10 @@ extern "C" int ronk_msm_bn254(const uint64_t* points, const uint64_t* scalars, s
   if (!out || (n && (!points || !scalars))) return RONK_ERR_INVALID;
   RCHK(need_device());
   if (n == 0) { for (int i = 0; i < 8; i++) out[i] = 0; return RONK_OK; }
-  DevBuf dp, ds;
-  RCHK(dp.alloc(n * 64)); RCHK(ds.alloc(n * 32));
-  HIPCHK(hipMemcpy(dp.p, points, n * 64, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(ds.p, scalars, n * 32, hipMemcpyHostToDevice));
-  return msm_run(dp.u(), ds.u(), n, out, 0);
+  HostCall hc;
+  const u64 *dp = hc.in(points, 8 * n), *ds = hc.in(scalars, 4 * n);
+  RCHK(hc.rc);
+  return ronk_msm_bn254_dev(dp, ds, n, out, nullptr);
 }
 
 // ------------------------------------------------------------------------------ kzg::open over BN254 (src/kzg/setup.rs:63-78)
@@ -246,10 +245,11 @@ extern "C" int ronk_kzg_open_bn254_dev(const uint64_t* d_coeffs, size_t n, const
   if (!d_coeffs || !z || !d_srs || !d_quot || !out_point || n == 0) return RONK_ERR_INVALID;
   if (n > ((size_t)1 << 30)) return RONK_ERR_UNSUPPORTED;
   RCHK(need_device());
-  DevBuf drem;
-  RCHK(drem.alloc(32));
-  RCHK(fr_div_linear_run(d_coeffs, n, z, d_quot, drem.u(), (hipStream_t)stream));
-  if (out_value) HIPCHK(hipMemcpy(out_value, drem.p, 32, hipMemcpyDeviceToHost));
+  HostCall hc;
+  u64* drem = hc.out(4);
+  RCHK(hc.rc);
+  RCHK(fr_div_linear_run(d_coeffs, n, z, d_quot, drem, (hipStream_t)stream));
+  if (out_value) RCHK(hc.get(out_value, drem, 32));
   return msm_run(d_srs, d_quot, n, out_point, (hipStream_t)stream);
 }
 extern "C" int ronk_kzg_open_bn254(const uint64_t* coeffs, size_t n, const uint64_t* z, const uint64_t* srs, size_t n_srs,
@@ -257,9 +257,9 @@ extern "C" int ronk_kzg_open_bn254(const uint64_t* coeffs, size_t n, const uint6
   if (!coeffs || !z || !srs || !out_point || n == 0) return RONK_ERR_INVALID;
   if (n_srs < n) return RONK_ERR_INDEX;                      // assert!(g1_srs.len() >= coeffs.len()), setup.rs:53
   RCHK(need_device());
-  DevBuf dc, dsrs, dq;
-  RCHK(dc.alloc(n * 32)); RCHK(dsrs.alloc(n * 64)); RCHK(dq.alloc(n * 32));
-  HIPCHK(hipMemcpy(dc.p, coeffs, n * 32, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dsrs.p, srs, n * 64, hipMemcpyHostToDevice));
-  return ronk_kzg_open_bn254_dev(dc.u(), n, z, dsrs.u(), dq.u(), out_point, out_value, 0);
+  HostCall hc;
+  const u64 *dc = hc.in(coeffs, 4 * n), *dsrs = hc.in(srs, 8 * n);
+  u64* dq = hc.out(4 * n);
+  RCHK(hc.rc);
+  return ronk_kzg_open_bn254_dev(dc, n, z, dsrs, dq, out_point, out_value, 0);
 }

@@ -214,19 +214,17 @@ static int mp_eval_form(u64 p, size_t d, size_t m, MpForm* f) {
 }
 
 static int mp_eval_run(u64 p, const u64* d_c, size_t d, const u64* d_xs, size_t m, u64* d_out, hipStream_t s, const MpForm& fm) {
-  if (roots_capturing(s)) return RONK_ERR_UNSUPPORTED;
+  if (stream_capturing(s)) return RONK_ERR_UNSUPPORTED;
   if (fm.form == FORM_DIRECT) return mp_eval_direct(p, d_c, d, d_xs, m, d_out, s);
   const size_t M = roots_padded(m, RONK_ROOTS_LEAF), Lp = pow2_at_least(d > M ? d : M);
   std::lock_guard<std::mutex> lk(g_roots_mu);
   RootsPins pins;
   pins.s = s;
-  void* lease = nullptr;
-  u64* ws = nullptr;
-  RCHK(ws_lease_acquire(mp_eval_ws_words(M, Lp) * 8, s, &lease, &ws));
-  struct Release { void* l; ~Release() { ws_lease_release(l); } } release{lease};
+  WsLease ws;
+  RCHK(ws.acquire(mp_eval_ws_words(M, Lp) * 8, s));
   MpTree t;
   t.fc = roots_consts(p); t.fld = fm.fld; t.p = p; t.gtree = fm.gtree; t.gz = fm.gz;
-  t.carve(ws, m, M);
+  t.carve(ws.u(), m, M);
   RCHK(roots_tree(t.fc, p, t.gtree, d_xs, m, t.z, t.tree_ws, pins, s, &t.keep));
   return mp_walk_down(t, d_c, d, d_xs, d_out, pins, s);
 }
@@ -245,13 +243,12 @@ extern "C" int ronk_poly_eval_many(uint64_t p, const uint64_t* c, size_t d, cons
   MpForm fm;
   RCHK(mp_eval_form(p, d, m, &fm));
   RCHK(need_device());
-  DevBuf dc, dx, dout;
-  RCHK(dc.alloc(d * 8)); RCHK(dx.alloc(m * 8)); RCHK(dout.alloc(m * 8));
-  HIPCHK(hipMemcpy(dc.p, c, d * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dx.p, xs, m * 8, hipMemcpyHostToDevice));
-  RCHK(mp_eval_run(p, dc.u(), d, dx.u(), m, dout.u(), nullptr, fm));
-  HIPCHK(hipMemcpy(out, dout.p, m * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64 *dc = hc.in(c, d), *dx = hc.in(xs, m);
+  u64* dout = hc.out(m);
+  RCHK(hc.rc);
+  RCHK(mp_eval_run(p, dc, d, dx, m, dout, nullptr, fm));   // the _dev form past its checks: the form is decided once per call
+  return hc.get(out, dout, m * 8);
 }
 
 // ------------------------------------------------------------------------------------- interpolation
@@ -271,14 +268,12 @@ static int mp_interp_form(u64 p, size_t m, MpForm* f) {
 // (the "not a geometric sequence" bit of its O(k log k) attempt, which Goldilocks calls of k >= 1024 make first, goes to a word
 // of its own) -- so any non-zero value is RONK_ERR_ZERO_INVERSE.
 static int mp_interp_direct(u64 p, const u64* d_xs, const u64* d_ys, size_t m, u64* d_out, int* d_status, hipStream_t s) {
-  void* lease = nullptr;
-  u64* ws = nullptr;
-  RCHK(ws_lease_acquire((2 * m + 8) * 8, s, &lease, &ws));
-  struct Release { void* l; ~Release() { ws_lease_release(l); } } release{lease};
-  u64* x = ws + 8;
-  u64* y = x + m;
-  int* flag = (int*)ws;
-  HIPCHK(hipMemsetAsync(ws, 0, 64, s));
+  WsLease ws;
+  RCHK(ws.acquire((2 * m + 8) * 8, s));
+  Carve c{ws.u()};
+  int* flag = (int*)c.take(8);
+  u64 *x = c.take(m), *y = c.take(m);
+  HIPCHK(hipMemsetAsync(flag, 0, 64, s));
   hipLaunchKernelGGL(mp_reduce_kernel, dim3(grid_for(m)), dim3(256), 0, s, p, d_xs, x, (u64)m);
   hipLaunchKernelGGL(mp_reduce_kernel, dim3(grid_for(m)), dim3(256), 0, s, p, d_ys, y, (u64)m);
   HIPCHK(hipGetLastError());
@@ -289,7 +284,7 @@ static int mp_interp_direct(u64 p, const u64* d_xs, const u64* d_ys, size_t m, u
 }
 
 static int mp_interp_run(u64 p, const u64* d_xs, const u64* d_ys, size_t m, u64* d_out, int* d_status, hipStream_t s, const MpForm& fm) {
-  if (roots_capturing(s)) return RONK_ERR_UNSUPPORTED;
+  if (stream_capturing(s)) return RONK_ERR_UNSUPPORTED;
   if (fm.form == FORM_DIRECT) return mp_interp_direct(p, d_xs, d_ys, m, d_out, d_status, s);
   const u64 gtree = fm.gtree;
   const u32 G = RONK_ROOTS_LEAF;
@@ -297,14 +292,12 @@ static int mp_interp_run(u64 p, const u64* d_xs, const u64* d_ys, size_t m, u64*
   std::lock_guard<std::mutex> lk(g_roots_mu);
   RootsPins pins;
   pins.s = s;
-  void* lease = nullptr;
-  u64* ws = nullptr;
   // the evaluation's workspace (d = m: Lp = M) and two more arrays of M: Z' and its values
-  RCHK(ws_lease_acquire((mp_eval_ws_words(M, M) + 2 * M) * 8, s, &lease, &ws));
-  struct Release { void* l; ~Release() { ws_lease_release(l); } } release{lease};
+  WsLease ws;
+  RCHK(ws.acquire((mp_eval_ws_words(M, M) + 2 * M) * 8, s));
   MpTree t;
   t.fc = roots_consts(p); t.fld = fm.fld; t.p = p; t.gtree = gtree; t.gz = fm.gz;
-  t.carve(ws, m, M);
+  t.carve(ws.u(), m, M);
   const FieldConst& fc = t.fc;
   u64* dz = t.newton + 10 * M;
   u64* dzx = dz + M;
@@ -367,14 +360,14 @@ extern "C" int ronk_poly_interpolate(uint64_t p, const uint64_t* xs, const uint6
   MpForm fm;
   RCHK(mp_interp_form(p, m, &fm));
   RCHK(need_device());
-  DevBuf dx, dy, dout, dst;
-  RCHK(dx.alloc(m * 8)); RCHK(dy.alloc(m * 8)); RCHK(dout.alloc(m * 8)); RCHK(dst.alloc(4));
-  HIPCHK(hipMemcpy(dx.p, xs, m * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dy.p, ys, m * 8, hipMemcpyHostToDevice));
-  RCHK(mp_interp_run(p, dx.u(), dy.u(), m, dout.u(), (int*)dst.p, nullptr, fm));
+  HostCall hc;
+  const u64 *dx = hc.in(xs, m), *dy = hc.in(ys, m);
+  u64* dout = hc.out(m);
+  int* dst = (int*)hc.out(1);   // (both forms write it themselves)
+  RCHK(hc.rc);
+  RCHK(mp_interp_run(p, dx, dy, m, dout, dst, nullptr, fm));
   int status = 0;
-  HIPCHK(hipMemcpy(&status, dst.p, 4, hipMemcpyDeviceToHost));
+  RCHK(hc.get(&status, dst, 4));
   if (status) return status;
-  HIPCHK(hipMemcpy(out, dout.p, m * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  return hc.get(out, dout, m * 8);
 }

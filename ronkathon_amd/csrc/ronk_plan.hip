@@ -3,7 +3,7 @@
 // what is built on it (fft / ifft / dft, polynomial multiply, batched Reed-Solomon encode).
 #include <map>
 
-#include "runtime.h"
+#include "workspace.h"
 #include "ntt_mul.h"
 #include "ntt_aux_kernels.h"
 #include "tile_select.h"
@@ -259,9 +259,7 @@ int transform_dev(ronk_plan* pl, bool inverse, const u64* in, const u64* in2, u6
   bool guard = false;
   if (uses_tmp && !tmp_override) {
     lk.lock();
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    guard = cap == hipStreamCaptureStatusNone;
+    guard = !stream_capturing(s);
     if (guard) scratch_acquire(pl, s);
   }
   int rc;
@@ -306,9 +304,7 @@ static int many_dev(ronk_plan* pl, bool inverse, const uint64_t* const* d_in, ui
   if (count == 0) return RONK_OK;
   for (size_t i = 0; i < count; i++) if (!d_in[i] || !d_out[i]) return RONK_ERR_INVALID;
   const CompiledPlan* cp = pl->fast ? &(inverse ? pl->inv : pl->fwd) : nullptr;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  if (pl->in_flight != 2 || !cp || count < 2 || cap != hipStreamCaptureStatusNone) {
+  if (pl->in_flight != 2 || !cp || count < 2 || stream_capturing(s)) {
     for (size_t i = 0; i < count; i++) RCHK(transform_dev(pl, inverse, d_in[i], nullptr, d_out[i], s));
     return RONK_OK;
   }
@@ -526,11 +522,11 @@ extern "C" int ronk_lagrange_nodes(uint64_t p, uint64_t g, uint64_t* nodes, size
   RCHK(need_device());
   FieldCtx f;
   RCHK(make_field(p, &f));
-  DevBuf d;
-  RCHK(d.alloc(n * 8));
-  RCHK(lagrange_nodes_dev(f, w, d.u(), n, 0));
-  HIPCHK(hipMemcpy(nodes, d.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  u64* d = hc.out(n);
+  RCHK(hc.rc);
+  RCHK(lagrange_nodes_dev(f, w, d, n, 0));
+  return hc.get(nodes, d, n * 8);
 }
 
 extern "C" int ronk_ntt_forward(ronk_plan* pl, const uint64_t* in, uint64_t* out, uint64_t* nodes) {
@@ -596,13 +592,8 @@ static uint64_t g_cache_clock = 0;
 // inside it (it would never complete for anybody else): a captured call skips both -- the graph then owns the entry's
 // scratch whenever it is replayed, like a captured transform owns its plan (transform_dev), and replays must not overlap other
 // users of the same product / transform size (include/ronk_ntt.h).
-static bool entry_capturing(hipStream_t s) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return cap != hipStreamCaptureStatusNone;
-}
-static hipError_t entry_wait(hipStream_t s, hipEvent_t ev) { return entry_capturing(s) ? hipSuccess : hipStreamWaitEvent(s, ev, 0); }
-static hipError_t entry_record(hipEvent_t ev, hipStream_t s) { return entry_capturing(s) ? hipSuccess : hipEventRecord(ev, s); }
+static hipError_t entry_wait(hipStream_t s, hipEvent_t ev) { return stream_capturing(s) ? hipSuccess : hipStreamWaitEvent(s, ev, 0); }
+static hipError_t entry_record(hipEvent_t ev, hipStream_t s) { return stream_capturing(s) ? hipSuccess : hipEventRecord(ev, s); }
 
 static void cache_entry_free(CacheEntry* e) {
   if (e->pl) ronk_plan_destroy(e->pl);
@@ -748,20 +739,13 @@ extern "C" int ronk_dft(uint64_t p, uint64_t g, const uint64_t* in, uint64_t* ou
   const bool chirp = p == RONK_GOLDILOCKS_P && g % p == RONK_GOLDILOCKS_G && n >= 512 && n <= ((size_t)1 << 29);
   if (!chirp && n > ((size_t)1 << 16)) return RONK_ERR_UNSUPPORTED;
   FieldCtx f;
-  RCHK(make_field(p, &f));
-  DevBuf di, dout;
-  RCHK(di.alloc(n * 8)); RCHK(dout.alloc(n * 8));
-  HIPCHK(hipMemcpy(di.p, in, n * 8, hipMemcpyHostToDevice));
-  if (chirp) {
-    RCHK(bluestein_dev(p, g % p, w, di.u(), dout.u(), n, 0));
-    HIPCHK(hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost));
-    return RONK_OK;
-  }
-  FIELD_DISPATCH(f, { hipLaunchKernelGGL((dft_naive_kernel<decltype(ops)>), dim3((u32)((n + 255) / 256)), dim3(256), 0, 0,
-                                        ops, di.u(), dout.u(), n, w); });
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  RCHK(make_field(p, &f));   // (like the size above: refused before anything is allocated)
+  HostCall hc;
+  const u64* di = hc.in(in, n);
+  u64* dout = hc.out(n);
+  RCHK(hc.rc);
+  RCHK(ronk_dft_dev(p, g, di, dout, n, nullptr));   // Bluestein or the direct kernel: the plan path was taken above
+  return hc.get(out, dout, n * 8);
 }
 
 // ------------------------------------------------------------------------------ polynomial multiply
@@ -899,12 +883,11 @@ extern "C" int ronk_poly_mul(uint64_t p, uint64_t g, const uint64_t* a, size_t d
   if (!a || !b || !out || d == 0 || d2 == 0) return RONK_ERR_INVALID;
   RCHK(need_device());
   const size_t m = d + d2 - 1;
-  DevBuf da, db, dout;
-  RCHK(da.alloc(d * 8)); RCHK(db.alloc(d2 * 8)); RCHK(dout.alloc(m * 8));
-  HIPCHK(hipMemcpy(da.p, a, d * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(db.p, b, d2 * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_poly_mul_dev(p, g, da.u(), d, db.u(), d2, dout.u(), 0));
-  HIPCHK(hipMemcpy(out, dout.p, m * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64 *da = hc.in(a, d), *db = hc.in(b, d2);
+  u64* dout = hc.out(m);
+  RCHK(hc.rc);
+  RCHK(ronk_poly_mul_dev(p, g, da, d, db, d2, dout, 0));
+  return hc.get(out, dout, m * 8);
 }
 

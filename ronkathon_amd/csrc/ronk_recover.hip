@@ -3,7 +3,6 @@
 // product tree").
 #include <map>
 
-#include "runtime.h"
 #include "roots_host.h"
 
 // ------------------------------------------------------------------------------------- kernels
@@ -219,19 +218,13 @@ int roots_field(u64 p, size_t m, u64* gtree) {
   return RONK_OK;
 }
 
-bool roots_capturing(hipStream_t s) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return st != hipStreamCaptureStatusNone;
-}
-
 extern "C" int ronk_poly_from_roots_dev(uint64_t p, const uint64_t* d_roots, size_t m, uint64_t* d_out, void* stream) {
   if (!d_out || (m && !d_roots)) return RONK_ERR_INVALID;
   u64 gtree = 0;
   RCHK(roots_field(p, m ? m : 1, &gtree));
   RCHK(need_device());
   hipStream_t s = (hipStream_t)stream;
-  if (roots_capturing(s)) return RONK_ERR_UNSUPPORTED;
+  if (stream_capturing(s)) return RONK_ERR_UNSUPPORTED;
   if (m == 0) {   // the empty product: ONE
     const u64 one = 1;
     HIPCHK(hipMemcpyAsync(d_out, &one, 8, hipMemcpyHostToDevice, s));
@@ -241,12 +234,9 @@ extern "C" int ronk_poly_from_roots_dev(uint64_t p, const uint64_t* d_roots, siz
   std::lock_guard<std::mutex> lk(g_roots_mu);
   RootsPins pins;
   pins.s = s;
-  void* lease = nullptr;
-  u64* ws = nullptr;
-  RCHK(ws_lease_acquire(roots_ws_words(m, roots_leaf()) * 8, s, &lease, &ws));
-  const int rc = roots_tree(fc, p, gtree, d_roots, m, d_out, ws, pins, s, nullptr);
-  ws_lease_release(lease);
-  return rc;
+  WsLease ws;
+  RCHK(ws.acquire(roots_ws_words(m, roots_leaf()) * 8, s));
+  return roots_tree(fc, p, gtree, d_roots, m, d_out, ws.u(), pins, s, nullptr);
 }
 
 extern "C" int ronk_poly_from_roots(uint64_t p, const uint64_t* roots, size_t m, uint64_t* out) {
@@ -254,12 +244,12 @@ extern "C" int ronk_poly_from_roots(uint64_t p, const uint64_t* roots, size_t m,
   u64 gtree = 0;
   RCHK(roots_field(p, m ? m : 1, &gtree));
   RCHK(need_device());
-  DevBuf dr, dout;
-  RCHK(dr.alloc(m * 8)); RCHK(dout.alloc((m + 1) * 8));
-  if (m) HIPCHK(hipMemcpy(dr.p, roots, m * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_poly_from_roots_dev(p, dr.u(), m, dout.u(), nullptr));
-  HIPCHK(hipMemcpy(out, dout.p, (m + 1) * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  HostCall hc;
+  const u64* dr = hc.in(roots, m);
+  u64* dout = hc.out(m + 1);
+  RCHK(hc.rc);
+  RCHK(ronk_poly_from_roots_dev(p, dr, m, dout, nullptr));
+  return hc.get(out, dout, (m + 1) * 8);
 }
 
 // ------------------------------------------------------------------------------------- erasure recovery
@@ -275,7 +265,7 @@ extern "C" int ronk_rs_recover_batch_dev(ronk_plan* plan, size_t k, const uint64
   if (k > N || n_erased > N - k) return RONK_ERR_INDEX;
   if (N < REC_CH || plan->field.kind == F_MOD2) return RONK_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (roots_capturing(s)) return RONK_ERR_UNSUPPORTED;
+  if (stream_capturing(s)) return RONK_ERR_UNSUPPORTED;
   const size_t e = n_erased;
   u64 gtree = 0, sh = 1, sinv = 1, omega = 1;
   if (e) {
@@ -299,10 +289,9 @@ extern "C" int ronk_rs_recover_batch_dev(ronk_plan* plan, size_t k, const uint64
   const size_t tree_w = e ? roots_ws_words(e, roots_leaf()) : 0;
   const size_t big = (size_t)B * N > tree_w ? (size_t)B * N : tree_w;
   const size_t bitmap_w = (N + 63) / 64;
-  void* lease = nullptr;
-  u64* ws = nullptr;
-  RCHK(ws_lease_acquire((8 + bitmap_w + (e ? 2 * N : 0) + big) * 8, s, &lease, &ws));
-  struct Release { void* l; ~Release() { ws_lease_release(l); } } release{lease};
+  WsLease lease;
+  RCHK(lease.acquire((8 + bitmap_w + (e ? 2 * N : 0) + big) * 8, s));
+  u64* ws = lease.u();
   int* err = (int*)ws;
   u32* bitmap = (u32*)(ws + 8);
   u64* zz = ws + 8 + bitmap_w;
@@ -358,15 +347,15 @@ extern "C" int ronk_rs_recover(uint64_t p, uint64_t g, size_t n, size_t k, const
   ronk_plan* pl = nullptr;
   RCHK(ronk_plan_create(&pl, p, g, (u32)ilog2(n), 1, -1));
   struct Destroy { ronk_plan* pl; ~Destroy() { ronk_plan_destroy(pl); } } destroy{pl};
-  DevBuf de, dy, dm, df, dst;
-  RCHK(de.alloc(n_erased * 8)); RCHK(dy.alloc(n * 8)); RCHK(dm.alloc(k * 8)); RCHK(df.alloc(n * 8)); RCHK(dst.alloc(4));
-  if (n_erased) HIPCHK(hipMemcpy(de.p, erased, n_erased * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dy.p, hy.data(), n * 8, hipMemcpyHostToDevice));
-  RCHK(ronk_rs_recover_batch_dev(pl, k, de.u(), n_erased, dy.u(), dm.u(), full ? df.u() : nullptr, (int*)dst.p, nullptr));
+  HostCall hc;
+  const u64 *de = hc.in(erased, n_erased), *dy = hc.in(hy.data(), n);
+  u64 *dm = hc.out(k), *df = hc.out(n);
+  int* dst = (int*)hc.out(1);   // (written by the call for every row: not zeroed here)
+  RCHK(hc.rc);
+  RCHK(ronk_rs_recover_batch_dev(pl, k, de, n_erased, dy, dm, full ? df : nullptr, dst, nullptr));
   int status = 0;
-  HIPCHK(hipMemcpy(&status, dst.p, 4, hipMemcpyDeviceToHost));
+  RCHK(hc.get(&status, dst, 4));
   if (status) return status;
-  HIPCHK(hipMemcpy(msg, dm.p, k * 8, hipMemcpyDeviceToHost));
-  if (full) HIPCHK(hipMemcpy(full, df.p, n * 8, hipMemcpyDeviceToHost));
-  return RONK_OK;
+  RCHK(hc.get(msg, dm, k * 8));
+  return full ? hc.get(full, df, n * 8) : RONK_OK;
 }

@@ -1,7 +1,7 @@
 // roots_host.h -- the host side of the product tree shared by ronk_recover.hip (which owns it) and ronk_multipoint.hip: the
 // field dispatch of the tree's kernels, the library-owned level plans with their pins, and the tree itself.
 #pragma once
-#include "runtime.h"
+#include "workspace.h"
 #include "roots_kernels.h"
 
 FieldConst roots_consts(u64 p);
@@ -58,6 +58,5 @@ u32 roots_leaf();
 size_t roots_padded(size_t m, u32 G);
 size_t roots_ws_words(size_t m, u32 G);
 int roots_field(u64 p, size_t m, u64* gtree);
-bool roots_capturing(hipStream_t s);
 int roots_tree(const FieldConst& fc, u64 p, u64 gtree, const u64* d_roots, size_t m, u64* d_out, u64* ws, RootsPins& pins,
                hipStream_t s, const RootsKeep* keep);

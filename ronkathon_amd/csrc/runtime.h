@@ -3,10 +3,13 @@
 //   ronk_core.hip     errors, device query, host integer logic, element-wise vector ops, device helpers
 //   ronk_plan.hip     plans, transforms, plan cache, fft/ifft/dft, polynomial multiply, batched RS encode
 //   ronk_callers.hip  evaluate, division, Lagrange evaluate, Reed-Solomon encode/decode, KZG commit (MSM)
+//   ronk_workspace.hip  the event-guarded workspace pool, its lease and the capture predicate (workspace.h)
 //   ronk_dist.hip     multi-GPU four-step phases
 //   ronk_recover.hip  the product tree and erasure recovery;  ronk_multipoint.hip  multipoint evaluation / interpolation on it
+//   ronk_hash.hip     Poseidon and Merkle;  ronk_msm.hip  BN254 MSM and kzg::open;  ronk_fr_ntt.hip  the BN254 scalar-field NTT
 //   ronk_ext2.hip, ronk_accum.hip, ronk_plonk.hip, ronk_pcs.hip, ronk_fri.hip  the extension-field family: one launch context and
-//                     dispatch (ext2_launch.h), host-pointer forms on HostCall (below)
+//                     dispatch (ext2_launch.h)
+// Every host-pointer entry point is a HostCall (below) around its _dev twin.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -38,11 +41,6 @@ int need_device();                              // RONK_OK or RONK_ERR_NO_DEVICE
     int rc_ = (call);         \
     if (rc_ != RONK_OK) return rc_; \
   } while (0)
-
-// ---- the event-guarded workspace pool (ronk_callers.hip): a lease of at least `bytes`, asynchronous on `s`; release it once
-//      the work that uses it has been queued
-int ws_lease_acquire(size_t bytes, hipStream_t s, void** lease, u64** ptr);
-void ws_lease_release(void* lease);
 
 // ---- the Newton series inverse on the NTT path (ronk_callers.hip): which fields it serves for products of up to 2 * 2^ceil(log2 d)
 //      points (and with which transform root), and the ladder itself
@@ -133,6 +131,14 @@ struct HostCall {
     }
     return d;
   }
+  int* status() {   // a zeroed device status word (read it back with get)
+    int* d = (int*)out(1);
+    if (d && rc == RONK_OK) {
+      hipError_t e = hipMemset(d, 0, 4);
+      if (e != hipSuccess) rc = hip_fail(e, "hipMemset");
+    }
+    return d;
+  }
   int get(void* h, const void* d, size_t bytes) const {
     HIPCHK(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
     return RONK_OK;
@@ -198,12 +204,7 @@ struct CompiledPlan {
              u64 out_valid = ~(u64)0, u64 in_poly_stride = 0, u64 x0_add = 0, u32 sb0 = 0, u32 sbn = 0,
              u64 in_valid1 = ~(u64)0) const {
     const PassDesc& ps = pd.passes[idx];
-    TileArgs a = ps.args;
-    const u64* bufs_in[3] = {in, out, tmp};
-    u64* bufs_out[3] = {nullptr, out, tmp};
-    a.in = bufs_in[ps.in_buf];
-    a.in2 = (ps.in_buf == BUF_IN) ? in2 : nullptr;
-    a.out = bufs_out[ps.out_buf];
+    TileArgs a = bound(idx, in, in2, out, tmp);
     if (ps.in_buf == BUF_IN) {
       a.in_valid = in_valid;
       a.in_valid1 = in_valid1;
@@ -212,9 +213,6 @@ struct CompiledPlan {
     if (ps.out_buf == BUF_OUT) a.out_valid = out_valid;
     if (x0_add && a.tw_log && a.xc) a.x0 += x0_add * a.xc;
     if (in_valid != ~(u64)0 || out_valid != ~(u64)0 || in_poly_stride) a.stage_io = 0;   // staged I/O copies whole tiles
-    a.wr = d_wr[ps.wr_id];
-    if (ps.tw_id >= 0) { a.tw_lo = d_tw[ps.tw_id].first; a.tw_hi = d_tw[ps.tw_id].second; }
-    if (ps.twf_id >= 0) a.tw_full = d_twf[ps.twf_id];
     u32 grid = ps.grid;
     if (sbn) {   // a slice of the batch axis b1: shift the three base pointers, shrink the grid
       a.in += (i64)sb0 * a.in_sb1;
