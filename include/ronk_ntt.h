@@ -826,6 +826,74 @@ int ronk_pcs_set_pow(ronk_pcs* pcs, uint32_t bits, uint32_t log2_limit);
 size_t ronk_pcs_handle_proof_words(const ronk_pcs* pcs);
 size_t ronk_pcs_handle_workspace_words(const ronk_pcs* pcs);
 
+/* ---- multi-matrix polynomial commitment: R matrices, committed one after the other (each round's challenges are drawn after the
+ *      previous commitment), each opened at its own subset of K extension points, combined into ONE DEEP codeword and opened under
+ *      ONE FRI.  The semantics are fixed here and restated on Python integers in tests/mpcs_ref.py.  Field, extension, domain
+ *      x_i = s w^i (i < N = 2^log2_n), transcript sponge, tree and FRI are those of the batched commitment above; A = 2^log2_arity,
+ *      m = N / A, D = digest_len, Q = n_queries.
+ *        shape     R = n_rounds matrices M_r, each [C_r][N] row-major base words, M_r[c][i] = f_(r,c)(x_i) with
+ *                  deg f < d = N >> log2_blowup; K = n_points extension points z, planar [2][K]; point_masks[r]: bit k set means
+ *                  round r is opened at z_k.  o_r = sum_(r' < r) C_r', C_tot = sum_r C_r.  All matrices share N and the blowup.
+ *        commit    per round exactly the batched commitment's leaf layout with C = C_r (leaf_len = C_r A, item_stride = 1,
+ *                  elem_stride = m): the tree that ronk_pcs_commit_dev writes on a handle of C_r columns.
+ *        claims    y[r][k][c] = f_(r,c)(z_k) for k in mask_r only, ordered by round, then by the set bits of the mask ascending,
+ *                  then by c; planar [2][Y], Y = sum_r popcount(mask_r) C_r.
+ *        transcript  a = sponge(seed || root_0 || .. || root_(R-1) || z c0 plane || z c1 plane || y c0 plane || y c1 plane)
+ *                  squeezing D words; alpha = (a[0], a[1]); the FRI seed is a.  Masks and shapes are handle parameters, as C and K
+ *                  are above; binding the earlier rounds into `seed` is the caller's outer protocol.
+ *        codeword  G[i] = sum_r sum_(k in mask_r) sum_(c < C_r) alpha^(k C_tot + o_r + c) (M_r[c][i] - y[r][k][c]) / (x_i - z_k),
+ *                  planar [2][N], canonical: every (r, k, c) term has a power of alpha of its own.  A z_k on the domain
+ *                  contributes zero and sets status bit 32.  For R = 1 with the full mask this is the codeword above, and
+ *                  transcript, proof layout and proof words are those of ronk_pcs_*.
+ *        proof     canonical words: [2][Y] claims; the extension FRI proof (input_ext = 1; with the nonce when grinding is set);
+ *                  then for each round in turn [Q][C_r A] leaf values and [Q][log2 m][D] paths.
+ *        verifier  from the [R][D] roots, z, the seed and the proof; it never sees a matrix.  Status bits 1 / 2 / 4 (64) as FRI
+ *                  reports them, 8 a matrix path of any round fails, 16 a DEEP mismatch, 32 some z_k on the domain.  Every check
+ *                  runs whatever the others find.
+ *        workspace D + Q words (a, open status), G [2][N], then the FRI workspace: that of ronk_pcs_workspace_words, whatever R.
+ *      ronk_mpcs_check (host integer logic): the codes of ronk_fri_check_ext with input_ext = 1; then RONK_ERR_INVALID for a NULL
+ *      array, n_points = 0, n_rounds = 0, some C_r = 0, some mask 0 or >= 2^n_points, or a point that no mask selects; then
+ *      RONK_ERR_UNSUPPORTED for n_points > 8, n_rounds > 8, C_tot > 1024 or log2_n < 2.  The size functions return 0 for refused
+ *      shapes.  d_M, d_tree and d_coef are HOST arrays of R device pointers, passed on to the kernels by value: there is no
+ *      device-side pointer table and no host round trip.  Every _dev call is asynchronous on `stream`, uses caller-owned
+ *      workspace and proof and no library workspace; one call at a time per handle.  The combination is one launch that reads
+ *      every matrix once and writes G only (csrc/mpcs_kernels.h).  ronk_mpcs_set_pow forwards to the embedded FRI handle as
+ *      ronk_pcs_set_pow does, and ronk_mpcs_open (host form) returns RONK_ERR_INDEX when the search finds nothing. */
+typedef struct ronk_mpcs ronk_mpcs;
+int ronk_mpcs_check(uint64_t p, uint32_t rate, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift, uint32_t log2_arity,
+                    uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len, uint32_t n_points,
+                    uint32_t n_rounds, const uint32_t* n_columns, const uint32_t* point_masks);
+size_t ronk_mpcs_proof_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len,
+                             uint32_t n_points, uint32_t n_rounds, const uint32_t* n_columns, const uint32_t* point_masks);
+size_t ronk_mpcs_workspace_words(uint32_t log2_n, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len,
+                                 uint32_t n_points, uint32_t n_rounds, const uint32_t* n_columns, const uint32_t* point_masks);
+/* The handle owns an extension FRI handle with input_ext = 1, copies the two arrays and borrows `pos`, which must outlive it. */
+int ronk_mpcs_create(ronk_mpcs** out, const ronk_poseidon* pos, uint64_t g, uint64_t w, uint32_t log2_n, uint64_t coset_shift,
+                     uint32_t log2_arity, uint32_t log2_final, uint32_t log2_blowup, uint32_t n_queries, uint32_t digest_len,
+                     uint32_t n_points, uint32_t n_rounds, const uint32_t* n_columns, const uint32_t* point_masks);
+int ronk_mpcs_destroy(ronk_mpcs* mpcs);
+int ronk_mpcs_set_pow(ronk_mpcs* mpcs, uint32_t bits, uint32_t log2_limit);
+size_t ronk_mpcs_handle_proof_words(const ronk_mpcs* mpcs);
+size_t ronk_mpcs_handle_workspace_words(const ronk_mpcs* mpcs);
+/* The tree of round `round`'s matrix ([C_round][N]) into the caller-owned d_tree, ronk_merkle_tree_words(N / A, D) words. */
+int ronk_mpcs_commit_dev(const ronk_mpcs* mpcs, uint32_t round, const uint64_t* d_M, uint64_t* d_tree, void* stream);
+/* The codeword G as a building block: d_y planar [2][Y], d_alpha two words in device memory, d_G [2][N], *d_status 0 or 32. */
+int ronk_mpcs_combine_dev(const ronk_mpcs* mpcs, const uint64_t* const* d_M, const uint64_t* d_y, const uint64_t* d_z,
+                          const uint64_t* d_alpha, uint64_t* d_G, int* d_status, void* stream);
+/* d_tree[r]: what ronk_mpcs_commit_dev wrote for d_M[r]; d_coef[r]: [C_r][d]; d_z: [2][K]; d_seed: D words; d_work and d_proof:
+ * ronk_mpcs_workspace_words and ronk_mpcs_proof_words words (with grinding, the handle's sizes).  *d_status: 0 or 32. */
+int ronk_mpcs_open_dev(const ronk_mpcs* mpcs, const uint64_t* const* d_M, const uint64_t* const* d_tree, const uint64_t* const* d_coef,
+                       const uint64_t* d_z, const uint64_t* d_seed, uint64_t* d_work, uint64_t* d_proof, int* d_status, void* stream);
+/* d_roots: [R][D] words. */
+int ronk_mpcs_verify_dev(const ronk_mpcs* mpcs, const uint64_t* d_roots, const uint64_t* d_z, const uint64_t* d_seed,
+                         const uint64_t* d_proof, int* d_status, void* stream);
+/* Host-pointer forms, synchronous: M, tree and coef are arrays of R host pointers. */
+int ronk_mpcs_commit(const ronk_mpcs* mpcs, uint32_t round, const uint64_t* M, uint64_t* tree);
+int ronk_mpcs_open(const ronk_mpcs* mpcs, const uint64_t* const* M, const uint64_t* const* tree, const uint64_t* const* coef,
+                   const uint64_t* z, const uint64_t* seed, uint64_t* proof, int* status);
+int ronk_mpcs_verify(const ronk_mpcs* mpcs, const uint64_t* roots, const uint64_t* z, const uint64_t* seed, const uint64_t* proof,
+                     int* status);
+
 /* ---- the quadratic extension F_p[t] / (t^2 - w) of a 64-bit prime field: the reference's GaloisField<2, P>
  *      (src/algebra/field/extension/, arithmetic.rs, gf_101_2.rs; PlutoBaseFieldExtension is p = 101, w = 99 = -2).  An element
  *      is the pair (c0, c1) = c0 + c1 t, the reference's coeffs in increasing degree.  Arrays are PLANAR: n elements are [2][n]

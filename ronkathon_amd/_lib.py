@@ -217,6 +217,21 @@ _SIG = {
     "ronk_pcs_set_pow": (_int, [_vp, C.c_uint32, C.c_uint32]),
     "ronk_pcs_handle_proof_words": (_sz, [_vp]),
     "ronk_pcs_handle_workspace_words": (_sz, [_vp]),
+    "ronk_mpcs_check": (_int, [_u64, C.c_uint32, _u64, _u64, C.c_uint32, _u64] + [C.c_uint32] * 7 + [_vp, _vp]),
+    "ronk_mpcs_proof_words": (_sz, [C.c_uint32] * 7 + [_vp, _vp]),
+    "ronk_mpcs_workspace_words": (_sz, [C.c_uint32] * 7 + [_vp, _vp]),
+    "ronk_mpcs_create": (_int, [C.POINTER(_vp), _vp, _u64, _u64, C.c_uint32, _u64] + [C.c_uint32] * 7 + [_vp, _vp]),
+    "ronk_mpcs_destroy": (_int, [_vp]),
+    "ronk_mpcs_set_pow": (_int, [_vp, C.c_uint32, C.c_uint32]),
+    "ronk_mpcs_handle_proof_words": (_sz, [_vp]),
+    "ronk_mpcs_handle_workspace_words": (_sz, [_vp]),
+    "ronk_mpcs_commit_dev": (_int, [_vp, C.c_uint32, _vp, _vp, _vp]),
+    "ronk_mpcs_combine_dev": (_int, [_vp] * 8),
+    "ronk_mpcs_open_dev": (_int, [_vp] * 10),
+    "ronk_mpcs_verify_dev": (_int, [_vp] * 7),
+    "ronk_mpcs_commit": (_int, [_vp, C.c_uint32, _vp, _vp]),
+    "ronk_mpcs_open": (_int, [_vp] * 7 + [C.POINTER(_int)]),
+    "ronk_mpcs_verify": (_int, [_vp] * 5 + [C.POINTER(_int)]),
     "ronk_ext2_check": (_int, [_u64, _u64]),
     "ronk_ext2_vec_add_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "ronk_ext2_vec_sub_dev": (_int, [_u64, _u64, _vp, _vp, _vp, _sz, _vp]),
@@ -608,6 +623,116 @@ class PcsHandle:
         seed, proof = self._sized("the seed", seed, self.digest_len), self._sized("the proof", proof, self.proof_words)
         st = _int(-1)
         check(lib.ronk_pcs_verify(self.h, ptr(root), ptr(z), ptr(seed), ptr(proof), C.byref(st)))
+        return st.value
+
+
+def _u32s(values):
+    values = [int(v) for v in values]
+    return (C.c_uint32 * max(len(values), 1))(*values)
+
+
+def _ptrs(values):
+    """a host array of pointers from ints (device pointers) or numpy arrays (host pointers)"""
+    values = [v if isinstance(v, int) else ptr(v).value for v in values]
+    return (C.c_void_p * max(len(values), 1))(*values)
+
+
+class MpcsHandle:
+    """ronk_mpcs: the multi-matrix polynomial commitment (include/ronk_ntt.h): len(n_columns) matrices of n_columns[r] columns,
+    round r opened at the points whose bits are set in point_masks[r], one DEEP codeword, one FRI; on a PoseidonHandle, which it
+    borrows.  The _dev methods take raw device pointers (int; lists of them for the matrices, trees and coefficients) and enqueue
+    on `stream`; one call at a time per handle."""
+
+    def __init__(self, pos, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, n_points, n_columns,
+                 point_masks, pow_bits=0, pow_log2_limit=None):
+        self.h = _vp()
+        self.pos = pos      # keeps the Poseidon handle alive
+        n_columns, point_masks = [int(c) for c in n_columns], [int(m) for m in point_masks]
+        if len(n_columns) != len(point_masks):
+            raise RonkPanic(ERR_INVALID, "one mask per round")
+        self.rounds = len(n_columns)
+        cs, ms = _u32s(n_columns), _u32s(point_masks)
+        check(lib.ronk_mpcs_create(C.byref(self.h), pos.h, g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries,
+                                   digest_len, n_points, self.rounds, cs, ms))
+        shape = (log2_n, log2_arity, log2_final, n_queries, digest_len, n_points, self.rounds, cs, ms)
+        self.proof_words = lib.ronk_mpcs_proof_words(*shape)
+        self.workspace_words = lib.ronk_mpcs_workspace_words(*shape)
+        self.n, self.arity, self.digest_len = 1 << log2_n, 1 << log2_arity, digest_len
+        self.columns, self.masks, self.points, self.coeffs = n_columns, point_masks, n_points, (1 << log2_n) >> log2_blowup
+        self.claims = sum(bin(m).count("1") * c for c, m in zip(n_columns, point_masks))
+        self.tree_words = lib.ronk_merkle_tree_words(self.n >> log2_arity, digest_len)
+        self.pow_bits = 0
+        if pow_bits:
+            self.set_pow(pow_bits, pow_log2_limit)
+
+    def set_pow(self, bits, log2_limit=None):
+        """grinding in the embedded FRI (ronk_mpcs_set_pow), before the handle is used; bits = 0: none"""
+        if log2_limit is None:
+            log2_limit = pow_default_limit(self.pos.p, bits)
+        check(lib.ronk_mpcs_set_pow(self.h, bits, log2_limit))
+        self.pow_bits, self.pow_log2_limit = bits, log2_limit
+        self.proof_words = lib.ronk_mpcs_handle_proof_words(self.h)
+        self.workspace_words = lib.ronk_mpcs_handle_workspace_words(self.h)
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            lib.ronk_mpcs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _each(self, what, a):
+        a = list(a)
+        if len(a) != self.rounds:
+            raise RonkPanic(ERR_INVALID, "%s: one per round" % what)
+        return a
+
+    def combine_dev(self, d_M, d_y, d_z, d_alpha, d_G, d_status, stream=0):
+        check(lib.ronk_mpcs_combine_dev(self.h, _ptrs(self._each("the matrices", d_M)), d_y, d_z, d_alpha, d_G, d_status, stream))
+
+    def commit_dev(self, r, d_M, d_tree, stream=0):
+        check(lib.ronk_mpcs_commit_dev(self.h, r, d_M, d_tree, stream))
+
+    def open_dev(self, d_M, d_tree, d_coef, d_z, d_seed, d_work, d_proof, d_status, stream=0):
+        check(lib.ronk_mpcs_open_dev(self.h, _ptrs(self._each("the matrices", d_M)), _ptrs(self._each("the trees", d_tree)),
+                                     _ptrs(self._each("the coefficients", d_coef)), d_z, d_seed, d_work, d_proof, d_status, stream))
+
+    def verify_dev(self, d_roots, d_z, d_seed, d_proof, d_status, stream=0):
+        check(lib.ronk_mpcs_verify_dev(self.h, d_roots, d_z, d_seed, d_proof, d_status, stream))
+
+    def _sized(self, what, a, words):
+        a = arr(a)
+        if a.size != words:
+            raise RonkPanic(ERR_INVALID, "%s holds %d words" % (what, words))
+        return a
+
+    def commit(self, r, M):
+        """host matrix [n_columns[r]][2^log2_n] of round r -> its tree (the root is its last digest_len words)"""
+        if not 0 <= r < self.rounds:
+            raise RonkPanic(ERR_INVALID, "no such round")
+        M = self._sized("the matrix", M, self.columns[r] * self.n)
+        tree = np.empty(self.tree_words, dtype=np.uint64)
+        check(lib.ronk_mpcs_commit(self.h, r, ptr(M), ptr(tree)))
+        return tree
+
+    def open(self, M, tree, coef, z, seed):
+        """lists of the rounds' matrices, trees and coefficients -> (the proof, status 0 or 32); z: planar [2][n_points]"""
+        M = [self._sized("a matrix", a, c * self.n) for a, c in zip(self._each("the matrices", M), self.columns)]
+        tree = [self._sized("a tree", a, self.tree_words) for a in self._each("the trees", tree)]
+        coef = [self._sized("the coefficients", a, c * self.coeffs) for a, c in zip(self._each("the coefficients", coef), self.columns)]
+        z, seed = self._sized("the points", z, 2 * self.points), self._sized("the seed", seed, self.digest_len)
+        proof = np.empty(self.proof_words, dtype=np.uint64)
+        st = _int(-1)
+        check(lib.ronk_mpcs_open(self.h, _ptrs(M), _ptrs(tree), _ptrs(coef), ptr(z), ptr(seed), ptr(proof), C.byref(st)))
+        return proof, st.value
+
+    def verify(self, roots, z, seed, proof):
+        """roots: [rounds][digest_len]"""
+        roots, z = self._sized("the roots", roots, self.rounds * self.digest_len), self._sized("the points", z, 2 * self.points)
+        seed, proof = self._sized("the seed", seed, self.digest_len), self._sized("the proof", proof, self.proof_words)
+        st = _int(-1)
+        check(lib.ronk_mpcs_verify(self.h, ptr(roots), ptr(z), ptr(seed), ptr(proof), C.byref(st)))
         return st.value
 
 

@@ -5,7 +5,8 @@
 * KZG `open` quotient (reference src/kzg/setup.rs:63-78): poly / (x - z).
 * KZG `commit` / `open` (reference src/kzg/setup.rs:45-78): the multi-scalar multiplication over the SRS.
 * `Poseidon`, `PoseidonSponge` (reference src/hashes/poseidon) and `MerkleTree` (reference src/tree/merkle.rs, over the sponge).
-* `Fri` and `FriPcs` (no counterpart in the reference): FRI for one column, and the batched polynomial commitment on top of it.
+* `Fri`, `FriPcs` and `FriMultiPcs` (no counterpart in the reference): FRI for one column, the batched polynomial commitment on
+  top of it, and several committed matrices opened at per-matrix points under one FRI.
 """
 import ctypes as C
 
@@ -457,6 +458,45 @@ class FriPcs:
     def verify(self, root, z, seed, proof):
         """-> 0, or bits: 1 / 2 / 4 / 64 as FRI reports them, 8 a matrix path fails, 16 a DEEP mismatch, 32 a point on the domain"""
         return self.handle.verify(root, z, seed, proof)
+
+
+class FriMultiPcs:
+    """The multi-matrix polynomial commitment of include/ronk_ntt.h ("multi-matrix polynomial commitment"): len(columns) matrices,
+    committed round by round, round r opened at the points whose bits are set in masks[r] (bit k: the k-th of `points` points of
+    F_p[t] / (t^2 - w)), under ONE FRI.  sponge_params as for MerkleTree.  Host arrays in and out; drawing each round's challenges
+    after the previous commitment, and binding the earlier roots into the seed, are the caller's outer protocol."""
+
+    def __init__(self, sponge_params, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup, n_queries, digest_len, points, columns,
+                 masks, g=None, pow_bits=0, pow_log2_limit=None):
+        field = sponge_params[0]
+        self.field, self.w = field, w
+        self.poseidon = L.PoseidonHandle(field.ORDER, *sponge_params[1:])
+        self.handle = L.MpcsHandle(self.poseidon, field._G if g is None else g, w, log2_n, coset_shift, log2_arity, log2_final, log2_blowup,
+                                   n_queries, digest_len, points, columns, masks, pow_bits=pow_bits, pow_log2_limit=pow_log2_limit)
+
+    def commit(self, r, matrix):
+        """round r's [columns[r]][N] values -> its tree; root(tree) is the round's commitment"""
+        return self.handle.commit(r, matrix)
+
+    def root(self, tree):
+        return tree[-self.handle.digest_len:]
+
+    def evaluate(self, r, coeffs, z):
+        """round r's claims at ITS points, planar [2][popcount(masks[r]) columns[r]]; z: planar [2][points]"""
+        h = self.handle
+        z = L.arr(z)
+        ks = [k for k in range(h.points) if (h.masks[r] >> k) & 1]
+        zr = np.concatenate([z[ks], z[[h.points + k for k in ks]]])
+        return L.ext2_poly_eval_batch(self.field.ORDER, self.w, np.asarray(coeffs, dtype=np.uint64).reshape(h.columns[r], -1), zr)
+
+    def open(self, matrices, trees, coeffs, z, seed):
+        """-> (the proof, ronk_mpcs_proof_words canonical words, and the status: 0, or 32 when a point lies on the domain)"""
+        return self.handle.open(matrices, trees, coeffs, z, seed)
+
+    def verify(self, roots, z, seed, proof):
+        """roots: [rounds][digest_len] -> 0, or bits: 1 / 2 / 4 / 64 as FRI reports them, 8 a matrix path of some round fails, 16 a
+        DEEP mismatch, 32 a point on the domain"""
+        return self.handle.verify(roots, z, seed, proof)
 
 
 def _prefix(field, values, exclusive, w, base_fn, ext_fn):
