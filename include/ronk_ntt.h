@@ -1062,6 +1062,82 @@ int ronk_plonk_quotient_dev(const ronk_plonk* h, const uint64_t* d_wires, const 
 int ronk_plonk_quotient(const ronk_plonk* h, const uint64_t* wires, const uint64_t* sel, const uint64_t* sigma, const uint64_t* pi,
                         const uint64_t* Z, const uint64_t* alpha, const uint64_t* beta, const uint64_t* gamma, uint64_t* T);
 
+/* ---- constraint programs: a straight-line program over the columns of a trace, fixed at handle creation, evaluated at every row
+ *      of the evaluation coset in ONE kernel launch, which adds sum_j lambda_j C_j (divisor of C_j's kind) onto T.  It is the
+ *      general form of the two quotients above: a custom gate, a wider permutation, or a STARK AIR with "every row but the last"
+ *      transitions and first / last-row boundary constraints.  The semantics are fixed here and restated on Python integers in
+ *      tests/air_ref.py.
+ *        domain    that of a ronk_plonk handle (above): N, B, M = N B, x_i = s w_M^i in natural order, w_N = w_M^B, the extension
+ *                  F_p[t] / (t^2 - W) as planar pairs, Goldilocks on its own arithmetic and every other odd prime on the Montgomery
+ *                  policy.  The handle refuses s^M = 1, so x_i - 1, x_i - w_N^-1 and x_i^N - 1 never vanish: no status word.  Its
+ *                  label multipliers are unused.
+ *        inputs    all on the coset, any 64-bit words (reduced).  G <= 8 base groups, group g a [C_g][M] matrix with its own
+ *                  device pointer; base column indices are flat across the groups in order, sum C_g <= 64.  E <= 8 extension
+ *                  columns, each a planar [2][M] array with its own pointer.  d_base and d_ext are HOST arrays of device pointers
+ *                  (they travel to the kernel by value).  d_chal [n_chal][2], n_chal <= 32: the extension constants of the call.
+ *                  d_lambda [J][2], J <= 64: one weight per constraint.  d_T_in planar [2][M] or NULL for zero; d_T_out == d_T_in
+ *                  is allowed; d_T_out must not overlap anything else.
+ *        program   n_regs <= 16 registers, imm[n_imm] base immediates (n_imm <= 256), ops[n_ops] (n_ops <= 4096), one uint64_t
+ *                  per op: bits 0-7 the opcode, 8-15 dst, 16-39 operand a, 40-63 operand b.  An operand is 24 bits: bits 0-3 its
+ *                  kind, 4-11 its index, 12-23 rot, a signed 12-bit number.
+ *                    operand kinds   0 REG   register `index`
+ *                                    1 BASE  base column `index` at row (i + rot B) mod M
+ *                                    2 EXT   extension column `index` at row (i + rot B) mod M
+ *                                    3 CHAL  challenge `index`
+ *                                    4 IMM   immediate `index`
+ *                                    5 X     the point x_i as a base element (index 0)
+ *                                    rot is 0 for every kind but BASE and EXT, and |rot| < N.
+ *                    opcodes         0 MOV   dst <- a              (b is 0)
+ *                                    1 ADD   dst <- a + b
+ *                                    2 SUB   dst <- a - b
+ *                                    3 MUL   dst <- a b
+ *                                    4 NEG   dst <- -a             (b is 0)
+ *                                    5 EMIT  constraint j (the raw 24 bits of b, j < J) has the value a and the kind dst
+ *                  Every j is emitted exactly once, and a register is never read before it is written.  Every value is an
+ *                  extension element, a base word v being (v, 0): that is the whole semantics.  ronk_air_create infers statically
+ *                  which values are base elements (computed from BASE, IMM, X and such registers only) and runs base arithmetic on
+ *                  them; that changes instruction counts, never a word of output.
+ *        kinds     with w_l = w_N^(N-1) = w_N^-1, constraint j of value C_j adds to row i
+ *                    0 ALL          (holds on every row of H)         lambda_j C_j / (x_i^N - 1)
+ *                    1 FIRST        (holds on row 0)                  lambda_j C_j / (N (x_i - 1))
+ *                    2 LAST         (holds on row N - 1)              lambda_j C_j w_l / (N (x_i - w_l))
+ *                    3 EXCEPT_LAST  (holds on rows 0 .. N - 2)        lambda_j C_j (x_i - w_l) / (x_i^N - 1)
+ *                  T_out_i = T_in_i + the sum of these, canonical.  FIRST is the P2 / S L1 convention of the two quotients above.
+ *                  Degree is the caller's concern: T is a polynomial of degree below M only when every constraint's degree allows.
+ *      ronk_air_check (host-side integer logic, no device), in this order:
+ *        1. RONK_ERR_INVALID      ops == NULL, n_columns == NULL with n_groups > 0, n_ops == 0, n_constraints == 0, some C_g == 0;
+ *        2. RONK_ERR_UNSUPPORTED  a limit above is passed (n_groups, C_g, sum C_g, n_ext, n_chal, n_imm, n_regs, n_constraints,
+ *                                 n_ops), log2_n < 1 or log2_n > 28;
+ *        3. RONK_ERR_INVALID      the first op, in program order, with an unknown opcode or operand kind, an index out of range
+ *                                 (a register, a column, a challenge, an immediate; X with an index; dst >= n_regs; an EMIT kind
+ *                                 above 3), rot on an operand that is no column or |rot| >= N, b != 0 on MOV or NEG, a register
+ *                                 read before it is written, an EMIT with j >= J or a j emitted before; at the end, a j never emitted.
+ *      ronk_air_create gives these codes for the domain's log2_n, RONK_ERR_INVALID for a NULL out, domain or imm (with n_imm > 0),
+ *      and RONK_ERR_NO_DEVICE.  The handle BORROWS the domain, which must outlive it; it owns the typed tape and the immediates in
+ *      device memory.  ronk_air_quotient_dev: NULL pointers (d_T_in excepted; the arrays the program has none of excepted) are
+ *      RONK_ERR_INVALID before any device work; asynchronous on `stream`: one kernel launch, no library workspace, no host round
+ *      trip -- legal under stream capture.  ronk_air_quotient is the synchronous host-pointer form (base and ext: host arrays of
+ *      host pointers).
+ *      The verifier's side, host only: ronk_air_cells returns the number of distinct column cells the program reads and writes
+ *      the first `cap` of them to `cells` (NULL with cap 0 to ask for the count) as 24-bit operands (kind, index, rot) in first-use
+ *      order: cell k is what a verifier needs opened, column `index` at z w_N^rot.  ronk_air_eval_point runs the same program at
+ *      the extension point z with X = z, cell k = cell_values[k] (a pair; chal and lambda are host arrays here), and returns the sum
+ *      of the terms above with x_i replaced by z: what T(z) must equal.  RONK_ERR_INVALID for a NULL pointer or z^N = 1. */
+typedef struct ronk_air ronk_air;
+int ronk_air_check(uint32_t log2_n, uint32_t n_groups, const uint32_t* n_columns, uint32_t n_ext, uint32_t n_chal, uint32_t n_imm,
+                   uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops, uint32_t n_ops);
+int ronk_air_create(ronk_air** out, const ronk_plonk* domain, uint32_t n_groups, const uint32_t* n_columns, uint32_t n_ext,
+                    uint32_t n_chal, uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops, uint32_t n_ops,
+                    const uint64_t* imm);
+int ronk_air_destroy(ronk_air* h);
+int ronk_air_quotient_dev(const ronk_air* h, const uint64_t* const* d_base, const uint64_t* const* d_ext, const uint64_t* d_chal,
+                          const uint64_t* d_lambda, const uint64_t* d_T_in, uint64_t* d_T_out, void* stream);
+int ronk_air_quotient(const ronk_air* h, const uint64_t* const* base, const uint64_t* const* ext, const uint64_t* chal,
+                      const uint64_t* lambda, const uint64_t* T_in, uint64_t* T_out);
+uint32_t ronk_air_cells(const ronk_air* h, uint32_t* cells, uint32_t cap);
+int ronk_air_eval_point(const ronk_air* h, const uint64_t z[2], const uint64_t* cell_values, const uint64_t* chal,
+                        const uint64_t* lambda, uint64_t out[2]);
+
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);
 int ronk_dev_free(void* ptr);

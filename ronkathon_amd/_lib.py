@@ -267,6 +267,14 @@ _SIG = {
     "ronk_lookup_mult": (_int, [_u64, _vp, _sz, _vp, C.c_uint32, _sz, _int, _vp, _vp]),
     "ronk_logup_quotient_dev": (_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ronk_logup_quotient": (_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
+    "ronk_air_check": (_int, [C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32]),
+    "ronk_air_create": (_int, [C.POINTER(_vp), _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                               C.c_uint32, _vp]),
+    "ronk_air_destroy": (_int, [_vp]),
+    "ronk_air_quotient_dev": (_int, [_vp] * 8),
+    "ronk_air_quotient": (_int, [_vp] * 7),
+    "ronk_air_cells": (C.c_uint32, [_vp, _vp, C.c_uint32]),
+    "ronk_air_eval_point": (_int, [_vp] * 6),
     "ronk_plonk_check": (_int, [_u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
     "ronk_plonk_create": (_int, [C.POINTER(_vp), _u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
     "ronk_plonk_destroy": (_int, [_vp]),

@@ -626,3 +626,35 @@ def logup_quotient(field, g, w, log2_n, log2_blowup, coset_shift, vals, mult, S,
     finally:
         L.lib.ronk_plonk_destroy(h)
     return T
+
+
+def air_quotient(field, g, w, log2_n, log2_blowup, coset_shift, program, base, ext, chal, lam, T_in=None):
+    """A constraint program on the coset of plonk_quotient: program = (ops, imm, n_regs, n_constraints) as AirBuilder.assemble() gives
+    it (ronkathon_amd.air), base a list of groups [C_g][M], ext a list of planar [2][M] columns, chal and lam lists of pairs (one
+    weight per constraint), T_in planar [2][M] or None.  -> T_in + sum_j lam_j C_j (divisor of C_j's kind) row by row, planar [2][M]
+    (include/ronk_ntt.h "constraint programs")."""
+    ops, imm, n_regs, n_constraints = program
+    p, M = field.ORDER, 1 << (log2_n + log2_blowup)
+    groups = [_columns("a base group", m) for m in base]
+    cols = [_columns("an extension column", m) for m in ext]
+    t = None if T_in is None else _columns("T_in", T_in)
+    ch, la = L.arr([int(c) for e in chal for c in e]), L.arr([int(c) for e in lam for c in e])
+    if any(m.shape[1] != M for m in groups) or any(m.shape != (2, M) for m in cols) or (t is not None and t.shape != (2, M)) or \
+            la.size != 2 * n_constraints or ch.size != 2 * len(chal):
+        raise L.RonkPanic(L.ERR_INVALID, "base groups [C_g][M], extension columns and T_in [2][M], one pair per challenge and constraint")
+    d_ops, d_imm = L.arr([int(v) for v in ops]), L.arr([int(v) % p for v in imm])
+    n_columns = (C.c_uint32 * max(1, len(groups)))(*[m.shape[0] for m in groups])
+    pointers = lambda arrays: (C.c_void_p * max(1, len(arrays)))(*[a.ctypes.data for a in arrays])      # noqa: E731
+    dom, h = C.c_void_p(), C.c_void_p()
+    L.check(L.lib.ronk_plonk_create(C.byref(dom), p, g, w, log2_n, log2_blowup, coset_shift, (C.c_uint64 * 3)(1, 2, 3)))
+    try:
+        L.check(L.lib.ronk_air_create(C.byref(h), dom, len(groups), n_columns, len(cols), len(chal), d_imm.size, n_regs, n_constraints,
+                                      L.ptr(d_ops), d_ops.size, L.ptr(d_imm) if d_imm.size else None))
+        T = np.empty(2 * M, dtype=np.uint64)
+        L.check(L.lib.ronk_air_quotient(h, pointers(groups), pointers(cols), L.ptr(ch) if ch.size else None, L.ptr(la),
+                                        None if t is None else L.ptr(t), L.ptr(T)))
+    finally:
+        if h:
+            L.lib.ronk_air_destroy(h)
+        L.lib.ronk_plonk_destroy(dom)
+    return T
