@@ -1138,6 +1138,108 @@ uint32_t ronk_air_cells(const ronk_air* h, uint32_t* cells, uint32_t cap);
 int ronk_air_eval_point(const ronk_air* h, const uint64_t z[2], const uint64_t* cell_values, const uint64_t* chal,
                         const uint64_t* lambda, uint64_t out[2]);
 
+/* ---- STARK: trace columns into a proof and a proof into accept / reject, end to end on the device.  A ronk_stark handle joins the
+ *      stages above -- the low-degree extension, the Merkle commitment, the constraint-program quotient, the multi-matrix
+ *      commitment with its one FRI -- under one transcript, and adds the quotient split between them (csrc/stark_kernels.h).  The
+ *      semantics are fixed here and restated on Python integers in tests/stark_ref.py, which is normative; the device reproduces
+ *      it word for word.
+ *        domain    that of a ronk_plonk handle: N = 2^log2_n trace rows, B = 2^log2_blowup, M = N B, x_i = s w_M^i, s^M != 1.  The
+ *                  commitment domain is the SAME coset: the inner ronk_mpcs handle has log2_n = log2 M, coset_shift = s and
+ *                  log2_blowup as given, so one extension of a trace round is both the committed matrix and the AIR's columns.
+ *        rounds    R = n_rounds trace rounds, 1 <= R <= 4.  Round r is a [C_r][N] matrix of base words (below p) on H = <w_N>;
+ *                  its last 2 E_r rows are the planes of E_r extension columns, c0 and c1 adjacent, so the pair is a planar
+ *                  [2][M] array after extension.  The base part of round r (C_r - 2 E_r columns; none is allowed) is an AIR group,
+ *                  the groups in round order; base column indices are flat across the rounds and extension columns are numbered
+ *                  across the rounds in order.  The limits are those of ronk_air_check: sum of the base parts <= 64, sum E_r <= 8.
+ *        challenges   the AIR's d_chal, n_chal <= 32 pairs: first the n_pub pairs the caller supplies (the public inputs), then the
+ *                  n_draw[0] pairs drawn after round 0, then those after round 1, and so on; n_pub + sum n_draw[r] = n_chal.
+ *        transcript   D = digest_len, sponge the handle's one-shot Poseidon sponge, squeezed words canonical.
+ *                  t = sponge(seed[D] || pub as [n_pub][2] words) squeezing D words.  After the commitment of round r:
+ *                  out = sponge(t || root_r) squeezing D + 2 n_draw[r] words, and two more for r = R - 1; t = out[:D], the draws
+ *                  are the pairs that follow, and the extra last pair of round R - 1 is lambda.  The constraint weights are
+ *                  lambda_j = lambda^j, j < J (lambda_0 = 1).
+ *        quotient  T = ronk_air_quotient_dev on the extended rounds with T_in = NULL, planar [2][M].
+ *        split     c_j (j < M): the monomial coefficients of T as extension elements, from the inverse transform of each plane
+ *                  and the un-shift by s^-j.  Piece i < B is q_i(x) = sum_(k < N) c_(i N + k) x^k, so T(x) = sum_i x^(i N) q_i(x).
+ *                  The quotient round is the [2 B][N] coefficient matrix, row 2 i + pl = plane pl of q_i, committed on the coset
+ *                  like a trace round: it is round R of the inner commitment.
+ *        points    after root_Q: out = sponge(t || root_Q) squeezing D + 2 words, t = out[:D], zeta = (out[D], out[D + 1]).
+ *                  z_0 = zeta; for every distinct non-zero (rot mod N) in the order of ronk_air_cells, z_k = zeta w_N^(rot mod N).
+ *                  K points, K <= 8.  The mask of trace round r: bit 0 and the bits of the rotations at which one of its columns
+ *                  is read; the mask of the quotient round: bit 0.
+ *        opening   ronk_mpcs_open_dev on the R + 1 rounds at z with seed t; its claims are the values of every round's
+ *                  coefficient rows at the points of its mask (what ronk_ext2_poly_eval_batch_dev gives).
+ *        proof     canonical words: the [R + 1][D] roots, then the inner handle's proof.
+ *        verifier  rebuilds the transcript from seed, pub and the proof's roots, runs ronk_mpcs_verify_dev, then checks
+ *                  sum_i zeta^(i N) (y_Q[2 i] + t y_Q[2 i + 1]) = ronk_air_eval_point(zeta, cells, chal, lambda_j), where cell
+ *                  (BASE, flat index, rot) is that column's claim at the point of rot and cell (EXT, e, rot) is the c0-claim +
+ *                  t times the c1-claim of its two rows.
+ *        status    the inner bits 1 / 2 / 4 / 8 / 16 / 32 / 64 pass through; 128: zeta has a zero second word (such a zeta could
+ *                  lie on a base-field domain: prover and verifier both set the bit and the proof is rejected; probability about
+ *                  2^-64); 256: the out-of-domain identity fails, or cannot be evaluated because zeta^N = 1.  Every check runs
+ *                  whatever the others find.  Degree is the caller's concern: a program whose degree exceeds what B allows, or a
+ *                  trace that breaks a constraint, yields a proof that the verifier rejects with bit 256; the prover does not
+ *                  detect it.
+ *      ronk_stark_check (host integer logic, no device), in this order:
+ *        1. the codes of ronk_air_check for the program on the groups above with n_ext = sum E_r and n_chal as given;
+ *        2. the codes of ronk_mpcs_check on the derived shape (log2 M, s, the blowup, K points, the R + 1 rounds and their masks);
+ *        3. the codes of ronk_plonk_check for the domain;
+ *        4. RONK_ERR_INVALID for a NULL array, n_rounds = 0, some 2 E_r > C_r or n_pub + sum n_draw[r] != n_chal; then
+ *           RONK_ERR_UNSUPPORTED for n_rounds > 4 or K > 8.
+ *      Where step 4 would refuse the rounds, steps 1 to 3 run on what can be derived: the first four rounds, E_r clamped to
+ *      C_r / 2, at most eight points, and no round at all for a NULL array.
+ *      ronk_stark_create gives these codes, RONK_ERR_INVALID for a NULL out, pos or imm (with n_imm > 0), and RONK_ERR_NO_DEVICE.
+ *      The handle BORROWS pos, which must outlive it, and owns its ronk_plonk, ronk_air and ronk_mpcs handles and its transform
+ *      plans.  ronk_stark_set_pow forwards to ronk_mpcs_set_pow; the size functions follow it and return 0 for a NULL handle.
+ *        workspace caller-owned, ronk_stark_workspace_words words: t, the challenge table, lambda and the weights, zeta and the
+ *                  points; per round (the quotient last) the extended matrix [C][M], the coefficients [C][N] and the tree; T;
+ *                  the coset-basis scratch; the inner handle's workspace.
+ *      The prover is staged, so that a caller can build accumulator columns from drawn challenges.  Every stage is asynchronous on
+ *      `stream` with no host round trip; the trace words of a round are read, never written.
+ *        ronk_stark_begin_dev          t from d_seed (D words) and d_pub ([n_pub][2] words; NULL with n_pub = 0); starts a sequence.
+ *        ronk_stark_commit_round_dev   round r from d_evals ([C_r][N]): inverse transform, coset scaling, encode, tree, draws.
+ *                                      Rounds go in order, 0 .. R - 1.
+ *        ronk_stark_challenges_dev     the device address of the table in d_work ([n_chal][2] words; NULL for a NULL argument).  The
+ *                                      challenges of round r are valid in stream order after its commit, and are usable directly
+ *                                      as the d_alpha / d_beta / d_gamma of ronk_logup_sum_dev and ronk_perm_product_dev.
+ *        ronk_stark_finish_dev         quotient, split, the quotient round, the points, the opening; d_proof receives
+ *                                      ronk_stark_proof_words words, *d_status (device) 0 or the bits 32 and 128.
+ *        ronk_stark_prove_dev          begin, commit round 0, finish, for R = 1 (else RONK_ERR_INVALID).
+ *      One call sequence at a time per handle, on one workspace; a stage out of order, or on another workspace than begin's, is
+ *      RONK_ERR_INVALID, and so is a NULL pointer.
+ *      ronk_stark_verify_dev enqueues the transcript and the inner verifier on `stream`, synchronises the stream ONCE and runs the
+ *      out-of-domain check on the host (ronk_air_eval_point is host-only): it is synchronous, *status is a HOST int, and it is not
+ *      for stream capture.  ronk_stark_prove (R = 1) and ronk_stark_verify are the host-pointer forms; with grinding set,
+ *      ronk_stark_prove returns RONK_ERR_INDEX when the search finds nothing, as ronk_mpcs_open does. */
+typedef struct ronk_stark ronk_stark;
+int ronk_stark_check(uint64_t p, uint32_t rate, uint64_t g, uint64_t w, uint32_t log2_n, uint32_t log2_blowup, uint64_t coset_shift,
+                     uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len, uint32_t n_rounds,
+                     const uint32_t* n_columns, const uint32_t* n_ext, uint32_t n_pub, const uint32_t* n_draw, uint32_t n_chal,
+                     uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops, uint32_t n_ops);
+int ronk_stark_create(ronk_stark** out, const ronk_poseidon* pos, uint64_t g, uint64_t w, uint32_t log2_n, uint32_t log2_blowup,
+                      uint64_t coset_shift, uint32_t log2_arity, uint32_t log2_final, uint32_t n_queries, uint32_t digest_len,
+                      uint32_t n_rounds, const uint32_t* n_columns, const uint32_t* n_ext, uint32_t n_pub, const uint32_t* n_draw,
+                      uint32_t n_chal, uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops, uint32_t n_ops,
+                      const uint64_t* imm);
+int ronk_stark_destroy(ronk_stark* st);
+int ronk_stark_set_pow(ronk_stark* st, uint32_t bits, uint32_t log2_limit);
+size_t ronk_stark_proof_words(const ronk_stark* st);
+size_t ronk_stark_workspace_words(const ronk_stark* st);
+int ronk_stark_begin_dev(ronk_stark* st, const uint64_t* d_seed, const uint64_t* d_pub, uint64_t* d_work, void* stream);
+int ronk_stark_commit_round_dev(ronk_stark* st, uint32_t round, const uint64_t* d_evals, uint64_t* d_work, void* stream);
+const uint64_t* ronk_stark_challenges_dev(const ronk_stark* st, const uint64_t* d_work);
+/* The split as a building block: d_c planar [2][M], the inverse transform of each plane of T (c'_j = c_j s^j); d_coef [2 B][N]
+ * receives the pieces' coefficients c_(i N + k), d_msg [2 B][N] the same in the coset basis, c_(i N + k) s^k, which
+ * ronk_rs_encode_batch_dev on an M-point plan of batch 2 B turns into the quotient matrix.  One launch; outputs must not overlap d_c. */
+int ronk_stark_split_dev(const ronk_stark* st, const uint64_t* d_c, uint64_t* d_coef, uint64_t* d_msg, void* stream);
+int ronk_stark_finish_dev(ronk_stark* st, uint64_t* d_work, uint64_t* d_proof, int* d_status, void* stream);
+int ronk_stark_prove_dev(ronk_stark* st, const uint64_t* d_seed, const uint64_t* d_pub, const uint64_t* d_evals, uint64_t* d_work,
+                         uint64_t* d_proof, int* d_status, void* stream);
+int ronk_stark_verify_dev(ronk_stark* st, const uint64_t* d_seed, const uint64_t* d_pub, const uint64_t* d_proof, int* status,
+                          void* stream);
+int ronk_stark_prove(ronk_stark* st, const uint64_t* seed, const uint64_t* pub, const uint64_t* evals, uint64_t* proof, int* status);
+int ronk_stark_verify(ronk_stark* st, const uint64_t* seed, const uint64_t* pub, const uint64_t* proof, int* status);
+
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);
 int ronk_dev_free(void* ptr);

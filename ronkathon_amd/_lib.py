@@ -275,6 +275,23 @@ _SIG = {
     "ronk_air_quotient": (_int, [_vp] * 7),
     "ronk_air_cells": (C.c_uint32, [_vp, _vp, C.c_uint32]),
     "ronk_air_eval_point": (_int, [_vp] * 6),
+    "ronk_stark_check": (_int, [_u64, C.c_uint32, _u64, _u64, C.c_uint32, C.c_uint32, _u64] + [C.c_uint32] * 5 + [_vp, _vp, C.c_uint32, _vp]
+                         + [C.c_uint32] * 4 + [_vp, C.c_uint32]),
+    "ronk_stark_create": (_int, [C.POINTER(_vp), _vp, _u64, _u64, C.c_uint32, C.c_uint32, _u64] + [C.c_uint32] * 5
+                          + [_vp, _vp, C.c_uint32, _vp] + [C.c_uint32] * 4 + [_vp, C.c_uint32, _vp]),
+    "ronk_stark_destroy": (_int, [_vp]),
+    "ronk_stark_set_pow": (_int, [_vp, C.c_uint32, C.c_uint32]),
+    "ronk_stark_proof_words": (_sz, [_vp]),
+    "ronk_stark_workspace_words": (_sz, [_vp]),
+    "ronk_stark_begin_dev": (_int, [_vp] * 5),
+    "ronk_stark_commit_round_dev": (_int, [_vp, C.c_uint32, _vp, _vp, _vp]),
+    "ronk_stark_challenges_dev": (_vp, [_vp, _vp]),
+    "ronk_stark_finish_dev": (_int, [_vp] * 5),
+    "ronk_stark_split_dev": (_int, [_vp] * 5),
+    "ronk_stark_prove_dev": (_int, [_vp] * 8),
+    "ronk_stark_verify_dev": (_int, [_vp] * 4 + [C.POINTER(_int), _vp]),
+    "ronk_stark_prove": (_int, [_vp] * 5 + [C.POINTER(_int)]),
+    "ronk_stark_verify": (_int, [_vp] * 4 + [C.POINTER(_int)]),
     "ronk_plonk_check": (_int, [_u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
     "ronk_plonk_create": (_int, [C.POINTER(_vp), _u64, _u64, _u64, C.c_uint32, C.c_uint32, _u64, _pu]),
     "ronk_plonk_destroy": (_int, [_vp]),

@@ -658,3 +658,31 @@ def air_quotient(field, g, w, log2_n, log2_blowup, coset_shift, program, base, e
             L.lib.ronk_air_destroy(h)
         L.lib.ronk_plonk_destroy(dom)
     return T
+
+
+def stark_prove(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, program, trace, pub,
+                seed, pow_bits=0):
+    """A STARK proof of one trace round (include/ronk_ntt.h "STARK"): program = (ops, imm, n_regs, n_constraints) as
+    AirBuilder.assemble() gives it, trace [C][N] base columns on <omega_N>, pub the public pairs (the program's first challenges),
+    seed digest_len words.  -> (the proof, the prover's status: 0, or the bits 32 / 128)."""
+    from .stark import Stark
+    t = _columns("the trace", trace)
+    st = Stark(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, (t.shape[0],), (0,),
+               len(pub), (0,), program, pow_bits=pow_bits)
+    try:
+        return st.prove(seed, pub, t)
+    finally:
+        st.close()
+
+
+def stark_verify(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, program, n_columns,
+                 pub, seed, proof, pow_bits=0):
+    """-> the verifier's status for a proof of stark_prove on a trace of n_columns columns: 0 accepts; 256 means the out-of-domain
+    identity fails, the lower bits are those of the embedded commitment"""
+    from .stark import Stark
+    st = Stark(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, (n_columns,), (0,),
+               len(pub), (0,), program, pow_bits=pow_bits)
+    try:
+        return st.verify(seed, pub, proof)
+    finally:
+        st.close()
