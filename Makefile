@@ -5,7 +5,7 @@ HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude
 CSRC = ronkathon_amd/csrc
 LIB = ronkathon_amd/libronk_ntt.so
 OBJS = build/tile_kernels_wl.o build/tile_kernels_r4.o build/tile_kernels_mont.o build/tile_kernels_mont_feat.o build/tile_kernels_mont_mul.o build/tile_kernels.o build/tile_kernels_cfg.o build/tile_kernels_half.o build/tile_kernels_feat.o build/tile_kernels_mul.o build/tile_kernels_dist_mul.o build/small_kernels.o build/ronk_core.o build/ronk_plan.o build/ronk_callers.o build/ronk_workspace.o build/ronk_dist.o build/ronk_msm.o build/ronk_recover.o build/ronk_multipoint.o build/ronk_hash.o build/ronk_fr_ntt.o build/ronk_fri.o build/ronk_ext2.o build/ronk_pcs.o build/ronk_accum.o build/ronk_plonk.o build/ronk_pow.o build/ronk_lookup.o build/ronk_mpcs.o build/ronk_air.o build/ronk_stark.o
-HDRS = $(wildcard $(CSRC)/*.h) include/ronk_ntt.h
+HDRS = $(wildcard $(CSRC)/*.h) $(wildcard include/*.h)
 
 all: $(LIB) oracle
 $(LIB): $(OBJS)
@@ -21,7 +21,7 @@ clean:
 .PHONY: all oracle clean
 
 # Sanitizer builds of the host-side code: the oracle under ASan+UBSan, the field header and the
-# tile kernel body + planner (the host emulator; Goldilocks and Montgomery field policies, the R4 round structure; the scan and long-division bodies, the Poseidon / sponge / Merkle bodies, the multipoint bodies, the BN254 scalar-field transform's pass body, the FRI fold / transcript / verifier bodies, the quadratic extension and the extension FRI bodies, the DEEP combination and extension-point evaluation bodies, the multi-matrix combination bodies, the scan and accumulator bodies, the PLONK quotient bodies, the proof-of-work bodies over the search kernel's grid, the lookup multiplicity bodies in three lane orders and the logUp quotient bodies, the constraint-program interpreter, the STARK quotient split and transcript steps) under UBSan (ASan does not follow the emulator's ucontext fibers).
+# tile kernel body + planner (the host emulator; Goldilocks and Montgomery field policies, the R4 round structure; the scan and long-division bodies, the Poseidon / sponge / Merkle bodies, the multipoint bodies, the BN254 scalar-field transform's pass body, the FRI fold / transcript / verifier bodies, the quadratic extension and the extension FRI bodies, the DEEP combination and extension-point evaluation bodies, the multi-matrix combination bodies, the scan and accumulator bodies, the PLONK quotient bodies, the proof-of-work bodies over the search kernel's grid, the lookup multiplicity bodies in three lane orders and the logUp quotient bodies, the constraint-program interpreter with and without periodic columns and the host construction of their tables, the STARK quotient split and transcript steps) under UBSan (ASan does not follow the emulator's ucontext fibers).
 SAN = -g -O1 -fno-omit-frame-pointer -fno-sanitize-recover=all
 sanitize:
 	@mkdir -p build/san
@@ -45,6 +45,7 @@ sanitize:
 	g++ $(SAN) -std=c++17 -fsanitize=undefined -o build/san/emu_lookup tests/emu/emu_lookup.cpp
 	g++ $(SAN) -std=c++17 -fsanitize=undefined -o build/san/emu_air tests/emu/emu_air.cpp
 	g++ $(SAN) -std=c++17 -fsanitize=undefined -o build/san/emu_stark tests/emu/emu_stark.cpp
+	g++ $(SAN) -std=c++17 -fsanitize=undefined -o build/san/emu_air_per tests/emu/emu_air_per.cpp
 	./build/san/oracle_san
 	./build/san/bn254_san
 	./build/san/test_gl64_host
@@ -115,4 +116,9 @@ sanitize:
 	./build/san/emu_stark 0xFFFFFFFC00000001 10 | tail -1
 	./build/san/emu_stark 97 5 | tail -1
 	./build/san/emu_stark 17 3 | tail -1
+	./build/san/emu_air_per 18446744069414584321 7 7 | tail -1
+	./build/san/emu_air_per 18446744069414584321 7 11 | tail -1
+	./build/san/emu_air_per 0xFFFFFFFC00000001 10 10 | tail -1
+	./build/san/emu_air_per 97 5 5 | tail -1
+	./build/san/emu_air_per 17 3 3 | tail -1
 .PHONY: sanitize

@@ -1086,7 +1086,8 @@ int ronk_plonk_quotient(const ronk_plonk* h, const uint64_t* wires, const uint64
  *                                    3 CHAL  challenge `index`
  *                                    4 IMM   immediate `index`
  *                                    5 X     the point x_i as a base element (index 0)
- *                                    rot is 0 for every kind but BASE and EXT, and |rot| < N.
+ *                                    6 PER   periodic column `index` (below), a base element
+ *                                    rot is 0 for every kind but BASE, EXT and PER, and |rot| < N.
  *                    opcodes         0 MOV   dst <- a              (b is 0)
  *                                    1 ADD   dst <- a + b
  *                                    2 SUB   dst <- a - b
@@ -1104,16 +1105,32 @@ int ronk_plonk_quotient(const ronk_plonk* h, const uint64_t* wires, const uint64
  *                    3 EXCEPT_LAST  (holds on rows 0 .. N - 2)        lambda_j C_j (x_i - w_l) / (x_i^N - 1)
  *                  T_out_i = T_in_i + the sum of these, canonical.  FIRST is the P2 / S L1 convention of the two quotients above.
  *                  Degree is the caller's concern: T is a polynomial of degree below M only when every constraint's degree allows.
- *      ronk_air_check (host-side integer logic, no device), in this order:
+ *        periodic  n_per <= 16 columns that are part of the program, not inputs of a call: column k has the period
+ *                  P = 2^log2_period[k] <= N and the values vals_k[0 .. P - 1]; per_values is the concatenation of the vals_k, any
+ *                  64-bit words (reduced).  On H the column is vals_k[i mod P] at row i.  Its polynomial: with q_k of degree below P
+ *                  and q_k(w_P^j) = vals_k[j], w_P = w_N^(N/P), the column is c_k(x) = q_k(x^(N/P)), of degree below N.  On the
+ *                  coset, x_i w_N^rot = s w_M^(i + rot B) and (w_M^(N/P))^(P B) = 1, so the operand at row i with rotation rot is
+ *                  tab_k[(i + rot B) mod (P B)] with tab_k[j] = q_k(s^(N/P) w_M^(j N/P)), j < P B.  P = 1 is a constant.  The handle
+ *                  owns the tables, sum_k P_k B words of device memory built at creation (host integer arithmetic: the inverse
+ *                  transform of vals_k over <w_P>, the scaling by s^(j N/P), the transform of length P B), and keeps the
+ *                  coefficients of q_k on the host.  The verifier never needs a periodic column opened: ronk_air_cells does not
+ *                  list PER operands, and ronk_air_eval_point evaluates q_k((z w_N^rot)^(N/P)) itself.  tests/air_per_ref.py
+ *                  restates all of this and is normative for these words.
+ *      ronk_air_check_per (host-side integer logic, no device), in this order; ronk_air_check is the case n_per = 0:
  *        1. RONK_ERR_INVALID      ops == NULL, n_columns == NULL with n_groups > 0, n_ops == 0, n_constraints == 0, some C_g == 0;
  *        2. RONK_ERR_UNSUPPORTED  a limit above is passed (n_groups, C_g, sum C_g, n_ext, n_chal, n_imm, n_regs, n_constraints,
  *                                 n_ops), log2_n < 1 or log2_n > 28;
+ *        2a. RONK_ERR_UNSUPPORTED n_per > 16;
+ *        2b. RONK_ERR_UNSUPPORTED some log2_period[k] > log2_n;
+ *        2c. RONK_ERR_INVALID     log2_period == NULL with n_per > 0;
  *        3. RONK_ERR_INVALID      the first op, in program order, with an unknown opcode or operand kind, an index out of range
- *                                 (a register, a column, a challenge, an immediate; X with an index; dst >= n_regs; an EMIT kind
+ *                                 (a register, a column, a challenge, an immediate, a periodic column: index >= n_per; X with an
+ *                                 index; dst >= n_regs; an EMIT kind
  *                                 above 3), rot on an operand that is no column or |rot| >= N, b != 0 on MOV or NEG, a register
  *                                 read before it is written, an EMIT with j >= J or a j emitted before; at the end, a j never emitted.
- *      ronk_air_create gives these codes for the domain's log2_n, RONK_ERR_INVALID for a NULL out, domain or imm (with n_imm > 0),
- *      and RONK_ERR_NO_DEVICE.  The handle BORROWS the domain, which must outlive it; it owns the typed tape and the immediates in
+ *      ronk_air_create_per gives these codes for the domain's log2_n, RONK_ERR_INVALID for a NULL out, domain or imm (with
+ *      n_imm > 0) before them and for a NULL per_values (with n_per > 0) after them, and RONK_ERR_NO_DEVICE; ronk_air_create is
+ *      the case n_per = 0.  The handle BORROWS the domain, which must outlive it; it owns the typed tape and the immediates in
  *      device memory.  ronk_air_quotient_dev: NULL pointers (d_T_in excepted; the arrays the program has none of excepted) are
  *      RONK_ERR_INVALID before any device work; asynchronous on `stream`: one kernel launch, no library workspace, no host round
  *      trip -- legal under stream capture.  ronk_air_quotient is the synchronous host-pointer form (base and ext: host arrays of
@@ -1180,15 +1197,46 @@ int ronk_air_eval_point(const ronk_air* h, const uint64_t z[2], const uint64_t* 
  *                  whatever the others find.  Degree is the caller's concern: a program whose degree exceeds what B allows, or a
  *                  trace that breaks a constraint, yields a proof that the verifier rejects with bit 256; the prover does not
  *                  detect it.
- *      ronk_stark_check (host integer logic, no device), in this order:
- *        1. the codes of ronk_air_check for the program on the groups above with n_ext = sum E_r and n_chal as given;
- *        2. the codes of ronk_mpcs_check on the derived shape (log2 M, s, the blowup, K points, the R + 1 rounds and their masks);
+ *        fixed     n_fixed = C_F > 0 adds one preprocessed round: a [C_F][N] matrix of base words on H (no extension columns) that is
+ *                  part of the statement -- selectors, a table, a ROM -- committed once, outside any proof, and bound to a handle by
+ *                  its root.  It is AIR group 0: its columns take the flat base indices 0 .. C_F - 1 and the trace rounds follow;
+ *                  the limits of ronk_air_check count it.  In the inner commitment it is round 0, the trace rounds are rounds
+ *                  1 .. R and the quotient is round R + 1; its mask follows the rule of a trace round.  Transcript: after
+ *                  t = sponge(seed || pub), t = sponge(t || root_F) squeezing D words (the step of a trace round with no draw),
+ *                  then the rounds as above; the inner opening's root list starts with root_F.  The proof holds the [R + 1][D]
+ *                  roots of the trace rounds and the quotient, then the inner proof on R + 2 rounds: it does NOT carry root_F, the
+ *                  verifier uses its own, so a verifier that holds another root rejects with the bits the statuses above give
+ *                  (no new bit).  The verifier maps a cell (BASE, index < C_F, rot) to the fixed round's claim.  The quotient
+ *                  reads the fixed round's extension as d_base[0].  n_per periodic columns (log2_period, per_values) go to the
+ *                  program through ronk_air_create_per ("constraint programs": periodic): they are never committed or opened.
+ *                  tests/stark_fixed_ref.py restates this on top of tests/stark_ref.py and is normative for these words.
+ *                    ronk_stark_fixed_words         the words of d_fixed: the extended matrix [C_F][M], the coefficients [C_F][N], the
+ *                                                   tree (its last D words the root, as for every round), the coset-basis scratch
+ *                                                   [C_F][N].  0 for a NULL handle or C_F = 0.  ronk_stark_workspace_words does not
+ *                                                   count the fixed round.
+ *                    ronk_stark_fixed_commit_dev    d_evals [C_F][N] into the caller-owned d_fixed: the steps of
+ *                                                   ronk_stark_commit_round_dev without the draws; asynchronous, no host round trip.
+ *                    ronk_stark_fixed_root_dev      the address of the root inside d_fixed (NULL for a NULL argument or C_F = 0).
+ *                    ronk_stark_set_fixed_dev       the handle BORROWS the whole d_fixed: prover and verifier.
+ *                    ronk_stark_set_fixed_root_dev  the handle borrows D words: a verifier; its prover stages are RONK_ERR_INVALID.
+ *                  A setter replaces what an earlier one set and ends a sequence in flight.  With C_F > 0 and nothing set,
+ *                  ronk_stark_begin_dev and ronk_stark_verify_dev return RONK_ERR_INVALID; with C_F = 0 the setters, the commit
+ *                  and their host forms do.  ronk_stark_fixed_commit is the host-pointer form of the commit; ronk_stark_set_fixed
+ *                  copies a host buffer of ronk_stark_fixed_words words (root_only != 0: the D words of a root) to device memory
+ *                  that the handle then owns.
+ *      ronk_stark_check_fixed (host integer logic, no device), in this order; ronk_stark_check and ronk_stark_create are the case
+ *      n_fixed = n_per = 0, for which every word of every output is what it was without these arguments:
+ *        1. the codes of ronk_air_check_per for the program on the groups above (the fixed round first) with n_ext = sum E_r, n_chal,
+ *           n_per and log2_period as given;
+ *        2. the codes of ronk_mpcs_check on the derived shape (log2 M, s, the blowup, K points, the R + 1 rounds and their masks,
+ *           after the fixed round when there is one);
  *        3. the codes of ronk_plonk_check for the domain;
  *        4. RONK_ERR_INVALID for a NULL array, n_rounds = 0, some 2 E_r > C_r or n_pub + sum n_draw[r] != n_chal; then
  *           RONK_ERR_UNSUPPORTED for n_rounds > 4 or K > 8.
  *      Where step 4 would refuse the rounds, steps 1 to 3 run on what can be derived: the first four rounds, E_r clamped to
  *      C_r / 2, at most eight points, and no round at all for a NULL array.
- *      ronk_stark_create gives these codes, RONK_ERR_INVALID for a NULL out, pos or imm (with n_imm > 0), and RONK_ERR_NO_DEVICE.
+ *      ronk_stark_create_fixed gives these codes, RONK_ERR_INVALID for a NULL out, pos or imm (with n_imm > 0) before them and for a
+ *      NULL per_values (with n_per > 0) after them, and RONK_ERR_NO_DEVICE.
  *      The handle BORROWS pos, which must outlive it, and owns its ronk_plonk, ronk_air and ronk_mpcs handles and its transform
  *      plans.  ronk_stark_set_pow forwards to ronk_mpcs_set_pow; the size functions follow it and return 0 for a NULL handle.
  *        workspace caller-owned, ronk_stark_workspace_words words: t, the challenge table, lambda and the weights, zeta and the
@@ -1239,6 +1287,10 @@ int ronk_stark_verify_dev(ronk_stark* st, const uint64_t* d_seed, const uint64_t
                           void* stream);
 int ronk_stark_prove(ronk_stark* st, const uint64_t* seed, const uint64_t* pub, const uint64_t* evals, uint64_t* proof, int* status);
 int ronk_stark_verify(ronk_stark* st, const uint64_t* seed, const uint64_t* pub, const uint64_t* proof, int* status);
+
+/* The entry points of the periodic columns ("constraint programs": periodic) and of the fixed round ("STARK": fixed), whose semantics
+ * are stated above, are declared in a header of their own. */
+#include "ronk_ntt_fixed.h"
 
 /* ---- small device-memory helpers so a non-HIP host (ctypes, cgo, JNI) can stay device-resident ---- */
 int ronk_dev_alloc(void** ptr, size_t bytes);

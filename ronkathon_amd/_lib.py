@@ -306,13 +306,32 @@ _SIG = {
     "ronk_get_device": (_int, [C.POINTER(_int)]),
     "ronk_trim_workspace": (_int, []),
 }
-for _name, (_res, _args) in _SIG.items():
+# include/ronk_ntt_fixed.h: the periodic columns of a constraint program and the fixed round of the STARK
+_SIG_FIXED = {
+    "ronk_air_check_per": (_int, [C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_uint32,
+                                  C.c_uint32, _vp]),
+    "ronk_air_create_per": (_int, [C.POINTER(_vp), _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp,
+                                   C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
+    "ronk_stark_check_fixed": (_int, [_u64, C.c_uint32, _u64, _u64, C.c_uint32, C.c_uint32, _u64] + [C.c_uint32] * 5
+                               + [_vp, _vp, C.c_uint32, _vp] + [C.c_uint32] * 4 + [_vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    "ronk_stark_create_fixed": (_int, [C.POINTER(_vp), _vp, _u64, _u64, C.c_uint32, C.c_uint32, _u64] + [C.c_uint32] * 5
+                                + [_vp, _vp, C.c_uint32, _vp] + [C.c_uint32] * 4 + [_vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, _vp]),
+    "ronk_stark_fixed_words": (_sz, [_vp]),
+    "ronk_stark_fixed_commit_dev": (_int, [_vp] * 4),
+    "ronk_stark_fixed_root_dev": (_vp, [_vp, _vp]),
+    "ronk_stark_set_fixed_dev": (_int, [_vp, _vp]),
+    "ronk_stark_set_fixed_root_dev": (_int, [_vp, _vp]),
+    "ronk_stark_fixed_commit": (_int, [_vp] * 3),
+    "ronk_stark_set_fixed": (_int, [_vp, _vp, _int]),
+}
+for _name, (_res, _args) in list(_SIG.items()) + list(_SIG_FIXED.items()):
     if os.environ.get("RONK_LIB_PATH") and not hasattr(lib, _name):
         continue              # an older build in an A/B run may lack the newest entry points
     _f = getattr(lib, _name)  # AttributeError here = the library does not export a declared symbol
     _f.restype, _f.argtypes = _res, _args
 
-EXPORTS = sorted(_SIG)
+EXPORTS = sorted(_SIG)                  # what include/ronk_ntt.h itself declares
+EXPORTS_FIXED = sorted(_SIG_FIXED)      # what include/ronk_ntt_fixed.h declares
 
 
 def check(rc, detail=""):

@@ -6,13 +6,13 @@
     b.constrain(a - b.chal(0), FIRST)
     ops, imm, n_regs, n_constraints = b.assemble()
 
-Leaves are base(c, rot), ext(c, rot), chal(k), imm(v) and x; expressions support + - * and unary -, with Python integers taken as
+Leaves are base(c, rot), ext(c, rot), periodic(p, rot), chal(k), imm(v) and x; expressions support + - * and unary -, with Python integers taken as
 immediates.  Equal subexpressions are one node (a + b and b + a, a * b and b * a are equal) and are computed once; registers are
 allocated greedily in evaluation order and freed at the last use of a value.  A program that needs more than 16 live values
 raises AirError.  Pure Python: nothing here touches the device."""
 
 MOV, ADD, SUB, MUL, NEG, EMIT = range(6)
-REG, BASE, EXT, CHAL, IMM, X = range(6)
+REG, BASE, EXT, CHAL, IMM, X, PER = range(7)
 ALL, FIRST, LAST, EXCEPT_LAST = range(4)
 MAX_REGS, MAX_IMM, MAX_OPS, MAX_CONSTRAINTS = 16, 256, 4096, 64
 
@@ -64,6 +64,10 @@ class AirBuilder:
 
     def ext(self, c, rot=0):
         return self._leaf(operand(EXT, c, rot))
+
+    def periodic(self, p, rot=0):
+        """periodic column p of the handle (ronk_air_create_per): a base element"""
+        return self._leaf(operand(PER, p, rot))
 
     def chal(self, k):
         return self._leaf(operand(CHAL, k))

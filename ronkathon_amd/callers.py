@@ -628,11 +628,22 @@ def logup_quotient(field, g, w, log2_n, log2_blowup, coset_shift, vals, mult, S,
     return T
 
 
-def air_quotient(field, g, w, log2_n, log2_blowup, coset_shift, program, base, ext, chal, lam, T_in=None):
+def periodic_arrays(periodic):
+    """periodic: one list of values per periodic column, each of a power-of-two length -> (n_per, the log2 periods as a ctypes array,
+    the concatenated values); any words, the library reduces them"""
+    lens = [len(v) for v in periodic]
+    if any(n == 0 or n & (n - 1) for n in lens):
+        raise L.RonkPanic(L.ERR_INVALID, "the period of a periodic column is a power of two")
+    logs = (C.c_uint32 * max(1, len(lens)))(*[n.bit_length() - 1 for n in lens])
+    return len(lens), logs, L.arr([int(v) % 2**64 for vals in periodic for v in vals])
+
+
+def air_quotient(field, g, w, log2_n, log2_blowup, coset_shift, program, base, ext, chal, lam, T_in=None, periodic=()):
     """A constraint program on the coset of plonk_quotient: program = (ops, imm, n_regs, n_constraints) as AirBuilder.assemble() gives
     it (ronkathon_amd.air), base a list of groups [C_g][M], ext a list of planar [2][M] columns, chal and lam lists of pairs (one
-    weight per constraint), T_in planar [2][M] or None.  -> T_in + sum_j lam_j C_j (divisor of C_j's kind) row by row, planar [2][M]
-    (include/ronk_ntt.h "constraint programs")."""
+    weight per constraint), T_in planar [2][M] or None, periodic the values of the periodic columns (one list per column, its length
+    the period).  -> T_in + sum_j lam_j C_j (divisor of C_j's kind) row by row, planar [2][M] (include/ronk_ntt.h "constraint
+    programs")."""
     ops, imm, n_regs, n_constraints = program
     p, M = field.ORDER, 1 << (log2_n + log2_blowup)
     groups = [_columns("a base group", m) for m in base]
@@ -645,11 +656,16 @@ def air_quotient(field, g, w, log2_n, log2_blowup, coset_shift, program, base, e
     d_ops, d_imm = L.arr([int(v) for v in ops]), L.arr([int(v) % p for v in imm])
     n_columns = (C.c_uint32 * max(1, len(groups)))(*[m.shape[0] for m in groups])
     pointers = lambda arrays: (C.c_void_p * max(1, len(arrays)))(*[a.ctypes.data for a in arrays])      # noqa: E731
+    n_per, log2_period, per_values = periodic_arrays(periodic)
     dom, h = C.c_void_p(), C.c_void_p()
     L.check(L.lib.ronk_plonk_create(C.byref(dom), p, g, w, log2_n, log2_blowup, coset_shift, (C.c_uint64 * 3)(1, 2, 3)))
     try:
-        L.check(L.lib.ronk_air_create(C.byref(h), dom, len(groups), n_columns, len(cols), len(chal), d_imm.size, n_regs, n_constraints,
-                                      L.ptr(d_ops), d_ops.size, L.ptr(d_imm) if d_imm.size else None))
+        common = (C.byref(h), dom, len(groups), n_columns, len(cols), len(chal), d_imm.size, n_regs, n_constraints, L.ptr(d_ops), d_ops.size,
+                  L.ptr(d_imm) if d_imm.size else None)
+        if n_per:
+            L.check(L.lib.ronk_air_create_per(*common, n_per, log2_period, L.ptr(per_values)))
+        else:
+            L.check(L.lib.ronk_air_create(*common))
         T = np.empty(2 * M, dtype=np.uint64)
         L.check(L.lib.ronk_air_quotient(h, pointers(groups), pointers(cols), L.ptr(ch) if ch.size else None, L.ptr(la),
                                         None if t is None else L.ptr(t), L.ptr(T)))
@@ -660,29 +676,44 @@ def air_quotient(field, g, w, log2_n, log2_blowup, coset_shift, program, base, e
     return T
 
 
+def _stark_fixed(st, fixed, root_only):
+    """commits the fixed columns [C_F][N] on st and binds them: the preprocessing a prover and a verifier each do for themselves"""
+    buf = st.fixed_commit(fixed)
+    at = st.fixed_root_offset
+    st.set_fixed(buf[at:at + st.digest_len] if root_only else buf, root_only=root_only)
+
+
 def stark_prove(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, program, trace, pub,
-                seed, pow_bits=0):
+                seed, pow_bits=0, fixed=None, periodic=()):
     """A STARK proof of one trace round (include/ronk_ntt.h "STARK"): program = (ops, imm, n_regs, n_constraints) as
     AirBuilder.assemble() gives it, trace [C][N] base columns on <omega_N>, pub the public pairs (the program's first challenges),
-    seed digest_len words.  -> (the proof, the prover's status: 0, or the bits 32 / 128)."""
+    seed digest_len words; fixed the [C_F][N] columns of the fixed round (the program's first base columns) or None, periodic the
+    values of the program's periodic columns.  -> (the proof, the prover's status: 0, or the bits 32 / 128)."""
     from .stark import Stark
     t = _columns("the trace", trace)
+    f = None if fixed is None else _columns("the fixed round", fixed)
     st = Stark(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, (t.shape[0],), (0,),
-               len(pub), (0,), program, pow_bits=pow_bits)
+               len(pub), (0,), program, pow_bits=pow_bits, n_fixed=0 if f is None else f.shape[0], periodic=periodic)
     try:
+        if f is not None:
+            _stark_fixed(st, f, False)
         return st.prove(seed, pub, t)
     finally:
         st.close()
 
 
 def stark_verify(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, program, n_columns,
-                 pub, seed, proof, pow_bits=0):
+                 pub, seed, proof, pow_bits=0, fixed=None, periodic=()):
     """-> the verifier's status for a proof of stark_prove on a trace of n_columns columns: 0 accepts; 256 means the out-of-domain
-    identity fails, the lower bits are those of the embedded commitment"""
+    identity fails, the lower bits are those of the embedded commitment.  fixed and periodic are the VERIFIER'S columns: it commits
+    its own fixed round and holds the root, so a proof made for other columns is rejected"""
     from .stark import Stark
+    f = None if fixed is None else _columns("the fixed round", fixed)
     st = Stark(sponge_params, g, w, log2_n, log2_blowup, coset_shift, log2_arity, log2_final, n_queries, digest_len, (n_columns,), (0,),
-               len(pub), (0,), program, pow_bits=pow_bits)
+               len(pub), (0,), program, pow_bits=pow_bits, n_fixed=0 if f is None else f.shape[0], periodic=periodic)
     try:
+        if f is not None:
+            _stark_fixed(st, f, True)
         return st.verify(seed, pub, proof)
     finally:
         st.close()

@@ -18,6 +18,11 @@
 // (deep_inverse) and unwound with Montgomery's trick before the loop, and parked in LDS behind the registers; a program without
 // those kinds skips all of it (a flag of the handle, wave-uniform).  ronk_plonk_check refuses s^M = 1, so nothing vanishes.
 //
+// A periodic column (operand kind PER) is never an input of a call: the handle owns its values on the coset, P B words per column
+// (the coset values of a column of period P repeat after P B rows), built once at creation by air_per_build below.  The kernel
+// reads the table's offset and mask at a wave-uniform index through the scalar path, then one word per lane, adjacent lanes
+// adjacent words.
+//
 // Plain C++ on uint64 behind a small accessor for the register file, so tests/emu/emu_air.cpp compiles the same bodies for the
 // host.
 #pragma once
@@ -28,11 +33,11 @@
 namespace ronk {
 
 constexpr u32 AIR_MAX_GROUPS = 8, AIR_MAX_BASE = 64, AIR_MAX_EXT = 8, AIR_MAX_CHAL = 32, AIR_MAX_IMM = 256, AIR_MAX_REGS = 16;
-constexpr u32 AIR_MAX_CONSTRAINTS = 64, AIR_MAX_OPS = 4096;
+constexpr u32 AIR_MAX_CONSTRAINTS = 64, AIR_MAX_OPS = 4096, AIR_MAX_PER = 16;
 constexpr u32 AIR_LANES = 256;              // lanes of a workgroup; halved while the LDS of a workgroup would pass AIR_LDS_MAX
 constexpr u32 AIR_LDS_MAX = 64 * 1024;
 enum AirOp : u32 { AIR_MOV, AIR_ADD, AIR_SUB, AIR_MUL, AIR_NEG, AIR_EMIT };
-enum AirOperand : u32 { AIR_REG, AIR_BASE, AIR_EXT, AIR_CHAL, AIR_IMM, AIR_X };
+enum AirOperand : u32 { AIR_REG, AIR_BASE, AIR_EXT, AIR_CHAL, AIR_IMM, AIR_X, AIR_PER };
 enum AirKind : u32 { AIR_ALL, AIR_FIRST, AIR_LAST, AIR_EXCEPT_LAST };
 
 // ---- the op word as the caller writes it (include/ronk_ntt.h)
@@ -46,7 +51,7 @@ RONK_HD int air_rot(u32 o) { return (int)(((o >> 12) & 0xfff) ^ 0x800) - 0x800; 
 
 // ---- the typed tape the kernel reads: the same fields with
 //        bits 0-2 the opcode, bit 3 operand a is an extension value, bit 4 operand b is, bits 5-6 the kind of an EMIT;
-//        an operand: bits 0-2 its kind, bits 3-11 its index (BASE: group << 6 | column in the group), bits 12-23 rot
+//        an operand: bits 0-2 its kind, bits 3-11 its index (BASE: group << 6 | column in the group; PER: the column p), bits 12-23 rot
 constexpr u64 AIR_TA = 8, AIR_TB = 16;
 
 // what the handle knows: device pointers, register form
@@ -56,6 +61,7 @@ struct AirProg {
   u32 n_ops, n_regs;
   u32 boundary;      // some constraint is FIRST or LAST
   u64 wl, wln;       // w_l = w_N^-1 and w_l / N
+  const u64* per;    // periodic columns: [n_per][2] words (offset from `per`, P B - 1), then the tables, register form; or NULL
 };
 // the arrays of a call
 struct AirCall {
@@ -111,6 +117,12 @@ RONK_HD E2 air_operand(const F& f, const AirProg& pg, const AirCall& c, const R&
       return E2{f.in(ch[2 * idx]), f.in(ch[2 * idx + 1])};
     }
     case AIR_IMM: return E2{((AirUniform)pg.imm)[idx], 0};
+    case AIR_PER: {
+      const AirUniform d = (AirUniform)pg.per;
+      const u64 off = d[2 * idx], mask = d[2 * idx + 1];
+      const int64_t by = (int64_t)air_rot(o) * ((int64_t)1 << log2b);
+      return E2{((FriTable)pg.per)[off + ((row + (u64)by) & mask)], 0};
+    }
     default: return E2{xi, 0};
   }
 }
@@ -204,10 +216,12 @@ struct AirShape {
   u32 log2n, n_groups;
   const u32* n_columns;   // [n_groups]
   u32 n_ext, n_chal, n_imm, n_regs, n_constraints;
+  u32 n_per = 0;
+  const u32* log2_period = nullptr;   // [n_per]
 };
 enum AirStatus { AIR_OK = 0, AIR_INVALID = 1, AIR_UNSUPPORTED = 2 };
 
-// The codes of ronk_air_check in their order.  With `tape` the typed tape, `boundary` and the cells (the distinct BASE and EXT
+// The codes of ronk_air_check_per in their order (ronk_air_check: n_per = 0).  With `tape` the typed tape, `boundary` and the cells (the distinct BASE and EXT
 // operands as the caller wrote them, in first-use order) are written as well.
 inline AirStatus air_compile(const AirShape& s, const u64* ops, u32 n_ops, std::vector<u64>* tape, u32* boundary,
                              std::vector<u32>* cells) {
@@ -222,6 +236,10 @@ inline AirStatus air_compile(const AirShape& s, const u64* ops, u32 n_ops, std::
   if (total > AIR_MAX_BASE || s.n_ext > AIR_MAX_EXT || s.n_chal > AIR_MAX_CHAL || s.n_imm > AIR_MAX_IMM || s.n_regs > AIR_MAX_REGS ||
       s.n_constraints > AIR_MAX_CONSTRAINTS || n_ops > AIR_MAX_OPS || s.log2n < 1 || s.log2n > PLONK_MAX_LOG2M)
     return AIR_UNSUPPORTED;
+  if (s.n_per > AIR_MAX_PER) return AIR_UNSUPPORTED;
+  for (u32 k = 0; k < s.n_per && s.log2_period; k++)
+    if (s.log2_period[k] > s.log2n) return AIR_UNSUPPORTED;
+  if (s.n_per && !s.log2_period) return AIR_INVALID;
   int rtype[AIR_MAX_REGS];
   for (u32 r = 0; r < AIR_MAX_REGS; r++) rtype[r] = -1;
   bool emitted[AIR_MAX_CONSTRAINTS] = {};
@@ -231,8 +249,8 @@ inline AirStatus air_compile(const AirShape& s, const u64* ops, u32 n_ops, std::
   auto operand = [&](u32 o, u32* typed, int* type) {
     const u32 kind = air_kind(o), idx = air_index(o);
     const int rot = air_rot(o);
-    if (kind > AIR_X) return false;
-    if (kind != AIR_BASE && kind != AIR_EXT && rot != 0) return false;
+    if (kind > AIR_PER) return false;
+    if (kind != AIR_BASE && kind != AIR_EXT && kind != AIR_PER && rot != 0) return false;
     if (rot >= N || -rot >= N) return false;
     u32 tidx = idx;
     switch (kind) {
@@ -251,6 +269,7 @@ inline AirStatus air_compile(const AirShape& s, const u64* ops, u32 n_ops, std::
       case AIR_EXT: if (idx >= s.n_ext) return false; *type = 1; break;
       case AIR_CHAL: if (idx >= s.n_chal) return false; *type = 1; break;
       case AIR_IMM: if (idx >= s.n_imm) return false; *type = 0; break;
+      case AIR_PER: if (idx >= s.n_per) return false; *type = 0; break;
       default: if (idx != 0) return false; *type = 0; break;
     }
     if (cells && (kind == AIR_BASE || kind == AIR_EXT)) {
@@ -293,6 +312,61 @@ inline AirStatus air_compile(const AirShape& s, const u64* ops, u32 n_ops, std::
   if (n_emitted != s.n_constraints) return AIR_INVALID;
   if (boundary) *boundary = bnd;
   return AIR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- host: the periodic columns
+// in-place transform of a[0 .. 2^log2len) on plain residues: a[k] <- sum_j a[j] root^(j k), root of order 2^log2len
+inline void air_host_ntt(u64 p, u64 root, u32 log2len, u64* a) {
+  const u64 n = (u64)1 << log2len;
+  for (u64 i = 1, j = 0; i < n; i++) {
+    u64 bit = n >> 1;
+    for (; j & bit; bit >>= 1) j ^= bit;
+    j ^= bit;
+    if (i < j) { const u64 t = a[i]; a[i] = a[j]; a[j] = t; }
+  }
+  for (u32 l = 1; l <= log2len; l++) {
+    const u64 half = (u64)1 << (l - 1), wl = fri_powmod(root, n >> l, p);
+    for (u64 b = 0; b < n; b += 2 * half) {
+      u64 w = 1 % p;
+      for (u64 k = 0; k < half; k++) {
+        const u64 u = a[b + k], v = fri_mulmod(a[b + k + half], w, p);
+        a[b + k] = (u64)(((unsigned __int128)u + v) % p);
+        a[b + k + half] = (u64)(((unsigned __int128)u + p - v) % p);
+        w = fri_mulmod(w, wl, p);
+      }
+    }
+  }
+}
+
+// Column k of period P = 2^log2_period[k] with the values vals (any words): q of degree below P with q(w_P^j) = vals[j], and
+// tab[j] = q(s^(N/P) w_M^(j N/P)), j < P B: the inverse transform over <w_P>, the scaling by (s^(N/P))^k, the zero padding to P B
+// and the transform over <w_M^(N/P)>.  coef receives the n_per coefficient vectors one after the other (plain residues, for the
+// evaluation at a point); words receives [n_per][2] (offset, mask) and then the tables in register form: what AirProg::per points to.
+inline void air_per_build(bool mont, u64 p, u64 g, u64 shift, u32 log2n, u32 log2b, u32 n_per, const u32* log2_period,
+                          const u64* vals, std::vector<u64>* coef, std::vector<u64>* words) {
+  coef->clear();
+  words->assign(2 * (size_t)n_per, 0);
+  for (u32 k = 0; k < n_per; k++) {
+    const u32 lp = log2_period[k];
+    const u64 P = (u64)1 << lp, PB = P << log2b;
+    std::vector<u64> q(P), t(PB, 0);
+    for (u64 j = 0; j < P; j++) q[j] = vals[j] % p;
+    vals += P;
+    const u64 wp = fri_powmod(g, (p - 1) >> lp, p), pinv = fri_powmod(P % p, p - 2, p);
+    air_host_ntt(p, fri_powmod(wp, p - 2, p), lp, q.data());
+    u64 sp = shift % p, run = 1 % p;
+    for (u32 j = lp; j < log2n; j++) sp = fri_mulmod(sp, sp, p);   // s^(N/P)
+    for (u64 j = 0; j < P; j++) {
+      q[j] = fri_mulmod(q[j], pinv, p);
+      t[j] = fri_mulmod(q[j], run, p);
+      run = fri_mulmod(run, sp, p);
+    }
+    air_host_ntt(p, fri_powmod(g, (p - 1) >> (lp + log2b), p), lp + log2b, t.data());
+    (*words)[2 * k] = words->size();
+    (*words)[2 * k + 1] = PB - 1;
+    for (u64 v : t) words->push_back(fri_reg_form(mont, p, v));
+    coef->insert(coef->end(), q.begin(), q.end());
+  }
 }
 
 // lanes of a workgroup and its LDS bytes for a program on PTS rows per lane

@@ -8,7 +8,7 @@
 
 struct ronk_plonk {
   u64 p = 0;
-  u64 g = 0, w = 0;        // plain: the generator (mod p) and W, for the host-side users of the domain (ronk_air.hip)
+  u64 g = 0, w = 0, s = 0; // plain: the generator (mod p), W and the coset shift, for the host-side users of the domain (ronk_air.hip)
   u32 log2m = 0;
   Ext2Launch c;            // the field policy, its constants, W
   DeepDomain dm{};

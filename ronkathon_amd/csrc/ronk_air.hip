@@ -13,40 +13,53 @@ struct ronk_air {
   AirProg pg{};
   u64* d_tape = nullptr;
   u64* d_imm = nullptr;
+  u64* d_per = nullptr;              // the descriptors and the coset tables of the periodic columns
   // the program as the caller wrote it, for the host-side evaluation
   std::vector<u64> ops, imm;         // imm reduced mod p
   std::vector<u32> cells, n_columns;
   u32 log2n = 0, n_ext = 0, n_chal = 0, n_constraints = 0;
+  std::vector<u32> log2_period;      // the periodic columns: column k has the coefficients per_coef[per_at[k] ..], plain residues
+  std::vector<u64> per_coef;
+  std::vector<size_t> per_at;
 };
 
 static int air_code(AirStatus s) { return s == AIR_OK ? RONK_OK : s == AIR_INVALID ? RONK_ERR_INVALID : RONK_ERR_UNSUPPORTED; }
 
+extern "C" int ronk_air_check_per(uint32_t log2_n, uint32_t n_groups, const uint32_t* n_columns, uint32_t n_ext, uint32_t n_chal,
+                                  uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops, uint32_t n_ops,
+                                  uint32_t n_per, const uint32_t* log2_period) {
+  const AirShape s{log2_n, n_groups, n_columns, n_ext, n_chal, n_imm, n_regs, n_constraints, n_per, log2_period};
+  return air_code(air_compile(s, ops, n_ops, nullptr, nullptr, nullptr));
+}
+
 extern "C" int ronk_air_check(uint32_t log2_n, uint32_t n_groups, const uint32_t* n_columns, uint32_t n_ext, uint32_t n_chal,
                               uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops, uint32_t n_ops) {
-  const AirShape s{log2_n, n_groups, n_columns, n_ext, n_chal, n_imm, n_regs, n_constraints};
-  return air_code(air_compile(s, ops, n_ops, nullptr, nullptr, nullptr));
+  return ronk_air_check_per(log2_n, n_groups, n_columns, n_ext, n_chal, n_imm, n_regs, n_constraints, ops, n_ops, 0, nullptr);
 }
 
 extern "C" int ronk_air_destroy(ronk_air* h) {
   if (!h) return RONK_ERR_INVALID;
   if (h->d_tape) (void)hipFree(h->d_tape);
   if (h->d_imm) (void)hipFree(h->d_imm);
+  if (h->d_per) (void)hipFree(h->d_per);
   delete h;
   return RONK_OK;
 }
 
-extern "C" int ronk_air_create(ronk_air** out, const ronk_plonk* domain, uint32_t n_groups, const uint32_t* n_columns, uint32_t n_ext,
-                               uint32_t n_chal, uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops,
-                               uint32_t n_ops, const uint64_t* imm) {
+extern "C" int ronk_air_create_per(ronk_air** out, const ronk_plonk* domain, uint32_t n_groups, const uint32_t* n_columns,
+                                   uint32_t n_ext, uint32_t n_chal, uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints,
+                                   const uint64_t* ops, uint32_t n_ops, const uint64_t* imm, uint32_t n_per,
+                                   const uint32_t* log2_period, const uint64_t* per_values) {
   if (!out) return RONK_ERR_INVALID;
   *out = nullptr;
   if (!domain || (n_imm && !imm)) return RONK_ERR_INVALID;
   const u32 log2n = domain->log2m - domain->tab.log2b;
-  const AirShape s{log2n, n_groups, n_columns, n_ext, n_chal, n_imm, n_regs, n_constraints};
+  const AirShape s{log2n, n_groups, n_columns, n_ext, n_chal, n_imm, n_regs, n_constraints, n_per, log2_period};
   std::vector<u64> tape;
   std::vector<u32> cells;
   u32 boundary = 0;
   RCHK(air_code(air_compile(s, ops, n_ops, &tape, &boundary, &cells)));
+  if (n_per && !per_values) return RONK_ERR_INVALID;
   RCHK(need_device());
   ronk_air* h = new ronk_air;
   const u64 p = domain->p;
@@ -60,14 +73,29 @@ extern "C" int ronk_air_create(ronk_air** out, const ronk_plonk* domain, uint32_
   for (u32 j = 0; j < n_imm; j++) { h->imm.push_back(imm[j] % p); reg[j] = ext2_reg_form(mont, p, imm[j]); }
   int rc = upload(tape, &h->d_tape);
   if (rc == RONK_OK) rc = upload(reg, &h->d_imm);
+  if (rc == RONK_OK && n_per) {
+    std::vector<u64> words;
+    air_per_build(mont, p, domain->g, domain->s, log2n, domain->tab.log2b, n_per, log2_period, per_values, &h->per_coef, &words);
+    h->log2_period.assign(log2_period, log2_period + n_per);
+    size_t at = 0;
+    for (u32 k = 0; k < n_per; k++) { h->per_at.push_back(at); at += (size_t)1 << log2_period[k]; }
+    rc = upload(words, &h->d_per);
+  }
   if (rc != RONK_OK) { ronk_air_destroy(h); return rc; }
   const u64 wn = h_powmod(domain->g, (p - 1) >> log2n, p), wl = h_powmod(wn, p - 2, p);
-  h->pg.tape = h->d_tape; h->pg.imm = h->d_imm;
+  h->pg.tape = h->d_tape; h->pg.imm = h->d_imm; h->pg.per = h->d_per;
   h->pg.n_ops = n_ops; h->pg.n_regs = n_regs; h->pg.boundary = boundary;
   h->pg.wl = ext2_reg_form(mont, p, wl);
   h->pg.wln = ext2_reg_form(mont, p, h_mulmod(wl, h_powmod(((u64)1 << log2n) % p, p - 2, p), p));
   *out = h;
   return RONK_OK;
+}
+
+extern "C" int ronk_air_create(ronk_air** out, const ronk_plonk* domain, uint32_t n_groups, const uint32_t* n_columns, uint32_t n_ext,
+                               uint32_t n_chal, uint32_t n_imm, uint32_t n_regs, uint32_t n_constraints, const uint64_t* ops,
+                               uint32_t n_ops, const uint64_t* imm) {
+  return ronk_air_create_per(out, domain, n_groups, n_columns, n_ext, n_chal, n_imm, n_regs, n_constraints, ops, n_ops, imm, 0, nullptr,
+                             nullptr);
 }
 
 // one launch with the rows per lane of the field policy, or one row per lane below that many rows (as plonk_launch); the LDS of a
@@ -162,9 +190,21 @@ extern "C" int ronk_air_eval_point(const ronk_air* h, const uint64_t z[2], const
   const u64 wn = h_powmod(h->dom->g, (p - 1) >> h->log2n, p), wl = h_powmod(wn, p - 2, p);
   const u64 ninv = h_powmod(((u64)1 << h->log2n) % p, p - 2, p);
   E2 reg[AIR_MAX_REGS] = {}, acc[4] = {};
+  // q_k((z w_N^rot)^(N/P)) by Horner's rule on the coefficients the handle keeps
+  auto periodic = [&](u32 k, int rot) {
+    const u64 N = (u64)1 << h->log2n, P = (u64)1 << h->log2_period[k];
+    const u64 turn = h_powmod(wn, (u64)((int64_t)rot + (int64_t)N) % N, p);
+    E2 y = x.mul(zz, E2{turn, 0});
+    for (u32 b = h->log2_period[k]; b < h->log2n; b++) y = x.mul(y, y);
+    const u64* q = h->per_coef.data() + h->per_at[k];
+    E2 r{0, 0};
+    for (u64 j = P; j-- > 0;) r = x.add(x.mul(r, y), E2{q[j], 0});
+    return r;
+  };
   auto operand = [&](u32 o) {
     const u32 kind = air_kind(o), idx = air_index(o);
     switch (kind) {
+      case AIR_PER: return periodic(idx, air_rot(o));
       case AIR_REG: return reg[idx];
       case AIR_CHAL: return E2{chal[2 * idx] % p, chal[2 * idx + 1] % p};
       case AIR_IMM: return E2{h->imm[idx], 0};

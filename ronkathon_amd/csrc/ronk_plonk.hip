@@ -34,7 +34,7 @@ extern "C" int ronk_plonk_create(ronk_plonk** out, uint64_t p, uint64_t g, uint6
   RCHK(ronk_plonk_check(p, g, w, log2_n, log2_blowup, coset_shift, k));
   RCHK(need_device());
   ronk_plonk* h = new ronk_plonk;
-  h->p = p; h->g = g % p; h->w = w % p; h->log2m = log2_n + log2_blowup;
+  h->p = p; h->g = g % p; h->w = w % p; h->s = coset_shift % p; h->log2m = log2_n + log2_blowup;
   h->c = ext2_launch(p, w);
   const bool mont = h->c.mont;
   const u32 kb = deep_kbits(h->log2m);
