@@ -121,4 +121,14 @@ sanitize:
 	./build/san/emu_air_per 0xFFFFFFFC00000001 10 10 | tail -1
 	./build/san/emu_air_per 97 5 5 | tail -1
 	./build/san/emu_air_per 17 3 3 | tail -1
+	# the emulators' directed mode (emu_ref.h): small signed words, which take the ">= p" outcomes of gl64.h all the time
+	RONK_EMU_SMALL=2 ./build/san/emu_poseidon 18446744069414584321 12 1 22 8 8 1 | tail -1
+	RONK_EMU_SMALL=2 ./build/san/emu_fri 18446744069414584321 7 | tail -1
+	RONK_EMU_SMALL=8 ./build/san/emu_ext2 18446744069414584321 7 | tail -1
+	RONK_EMU_SMALL=2 ./build/san/emu_deep 18446744069414584321 7 11 | tail -1
+	RONK_EMU_SMALL=2 ./build/san/emu_mpcs 18446744069414584321 7 | tail -1
+	RONK_EMU_SMALL=2 ./build/san/emu_accum 18446744069414584321 7 | tail -1
+	RONK_EMU_SMALL=2 ./build/san/emu_plonk 18446744069414584321 7 7 4 2 7 1 | tail -1
+	RONK_EMU_SMALL=2 ./build/san/emu_air 18446744069414584321 7 7 | tail -1
+	RONK_EMU_SMALL=2 ./build/san/emu_air_per 18446744069414584321 7 7 | tail -1
 .PHONY: sanitize

@@ -15,6 +15,7 @@
 #include "../../ronkathon_amd/csrc/accum_kernels.h"
 using namespace ronk;
 #include "emu_ref.h"
+#include "emu_census.h"
 
 // ---------------------------------------------------------------------------------------------------- the kernels, lane by lane
 template <class O>
@@ -87,6 +88,16 @@ static void run_scan(bool mont, u64 p, u64 w, size_t n, int exclusive, bool in_p
   const O op(ext2_host_consts(mont, p), ext2_reg_form(mont, p, w));
   std::vector<u64> a((size_t)EW * n), out((size_t)EW * n, ~(u64)0), work(acc_work_words(n), ~(u64)0), total(EW, ~(u64)0);
   for (auto& v : a) v = PROD && rnd() % 64 ? 1 + rnd() % (p - 1) : edge_word(p);   // few zeros in a product
+  if (PROD && emu_small()) {   // the directed mode: factors +-1 and a few 2's -- pairs: (+-1, 0) and a few t's, 1 + t's and 1 - t's,
+    size_t k = 0;              // whose products have two non-zero components -- so that every prefix stays small
+    for (size_t i = 0; i < n; i++) {
+      const bool special = i % (n / 16 + 1) == n / 32;
+      const int kind = !special ? 0 : EW == 1 ? (k < 10 ? 1 : 0) : k % 5 == 1 ? 2 : k % 5 == 3 ? 3 : 1;   // at most ten 2's, as in gl_directed.scan_base
+      k += special;
+      a[i] = kind == 0 ? (rnd() & 1 ? 1 : p - 1) : kind == 1 ? (EW == 2 ? 0 : 2) : 1;
+      if (EW == 2) a[n + i] = kind == 0 ? 0 : kind == 3 ? p - 1 : 1;
+    }
+  }
   // the restatement
   std::vector<R2> want(n);
   R2 run = PROD ? R2{1 % p, 0} : R2{0, 0};
@@ -98,9 +109,15 @@ static void run_scan(bool mont, u64 p, u64 w, size_t n, int exclusive, bool in_p
   }
   std::vector<u64> src = a;
   u64* o = in_place ? src.data() : out.data();
+  static const char* const stage[2][2][3] = {{{"scan_sum_base_1", "scan_sum_base_2", "scan_sum_base_3"}, {"scan_prod_base_1", "scan_prod_base_2", "scan_prod_base_3"}},
+                                            {{"scan_sum_ext_1", "scan_sum_ext_2", "scan_sum_ext_3"}, {"scan_prod_ext_1", "scan_prod_ext_2", "scan_prod_ext_3"}}};
+  census_stage(stage[EW - 1][PROD][0]);
   emu_phase1(op, src.data(), n, work.data());
+  census_stage(stage[EW - 1][PROD][1]);
   emu_phase2(op, work.data(), acc_blocks(n), total.data(), false);
+  census_stage(stage[EW - 1][PROD][2]);
   emu_phase3(op, src.data(), o, n, exclusive, work.data());
+  census_stage(nullptr);
   for (size_t i = 0; i < n; i++)
     CHECK(o[i] == want[i].c0 && (EW == 1 || o[n + i] == want[i].c1), "scan EW=%d prod=%d n=%zu excl=%d inplace=%d i=%zu", EW, (int)PROD, n,
           exclusive, (int)in_place, i);
@@ -309,9 +326,12 @@ int main(int argc, char** argv) {
   g_rng = p ^ w ^ 16;
   int policies = 0;
   if (p == gl64::P) {
+    census_policy("gl.");
     run_all<FriGl>(false, p, w); policies |= 1;
+    census_policy("w7.");
     if (w % p == 7) { run_all<FriGlW7>(false, p, w); policies |= 2; }
   }
+  census_policy("mont.");
   run_all<FriMont>(true, p, w); policies |= 4;
   if (g_fail) { printf("FAILED %d checks\n", g_fail); return 1; }
   printf("OK p=%llu w=%llu policies=%d\n", (unsigned long long)p, (unsigned long long)w, policies);

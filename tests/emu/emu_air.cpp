@@ -24,6 +24,7 @@
 #include "../../ronkathon_amd/csrc/air_kernels.h"
 using namespace ronk;
 #include "emu_ref.h"
+#include "emu_census.h"
 
 struct Shape {
   u64 p, g, w;
@@ -139,8 +140,10 @@ static std::vector<u64> emu_quotient(bool mont, const Shape& s, const Case& c) {
       CHECK(lds.back() == 0xDEADBEEFDEADBEEFull, "a lane wrote past its slots");
     }
   };
+  census_stage("air");   // (emu_census.h: the interpreter's lanes are the one body here)
   if (log2m < PlonkRows<F>::LOG2) run(std::integral_constant<int, 1>{});
   else run(std::integral_constant<int, 1 << PlonkRows<F>::LOG2>{});
+  census_stage(nullptr);
   for (u64 r = 0; r < M; r++) CHECK(written[r], "row %llu never written", (unsigned long long)r);
   return T;
 }
@@ -152,9 +155,12 @@ static int run_case(const Shape& s, const Case& c, std::vector<std::vector<u64>>
   int policies = 0;
   results.clear();
   if (p == gl64::P) {
+    census_policy("gl.");
     results.push_back(emu_quotient<FriGl>(false, s, c)); policies |= 1;
+    census_policy("w7.");
     if (s.w % p == 7) { results.push_back(emu_quotient<FriGlW7>(false, s, c)); policies |= 2; }
   }
+  census_policy("mont.");
   results.push_back(emu_quotient<FriMont>(true, s, c)); policies |= 4;
   CHECK(before.base == c.base && before.ext == c.ext && before.chal == c.chal && before.lam == c.lam && before.T_in == c.T_in,
         "an input changed");

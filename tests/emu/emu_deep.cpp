@@ -39,7 +39,7 @@ static void make_domain(Domain& D, bool mont, u64 p, u64 g, u64 shift, u32 n) {
   D.dm.lo = D.tab.data(); D.dm.hi = D.tab.data() + ((size_t)1 << kb); D.dm.kbits = kb; D.dm.log2n = n;
 }
 
-static u64 pair_word(u64 p, int c) { return c == 0 ? 0 : c == 1 ? 1 : c == 2 ? p - 1 : c == 3 ? p + 1 + rnd() % 3 : rnd() % p; }
+static u64 pair_word(u64 p, int c) { return c == 0 ? 0 : c == 1 ? 1 : c == 2 ? p - 1 : c == 3 ? p + 1 + rnd() % 3 : challenge_word(p); }
 
 template <class F, int K>
 static void run_combine(bool mont, u64 p, u64 g, u64 w) {
@@ -73,10 +73,12 @@ static void run_combine(bool mont, u64 p, u64 g, u64 w) {
           for (size_t j = 0; j < ys.size(); j++) { yw[j] = ys[j].c0; yw[ys.size() + j] = ys[j].c1; }
           const E2 a{f.in(aw[0]), f.in(aw[1])};
           int bits = 0;
+          census_stage("deep_prep");
           for (u32 c = 0; c < C; c++) deep_prep_column(x, a, c, tab.data() + (size_t)DEEP_KW * K);
           for (u32 j = 0; j < (u32)K; j++) bits |= deep_prep_point(x, D.dm, a, zw.data(), yw.data(), K, C, j, tab.data() + (size_t)DEEP_KW * j);
           CHECK(bits == (want_on ? 32 : 0), "status K=%d n=%u C=%u variant=%d bits=%d", K, n, C, variant, bits);
           const DeepTab T{tab.data(), tab.data() + (size_t)DEEP_KW * K};
+          census_stage(nullptr);
           // the restatement
           std::vector<R2> want(N);
           for (u64 i = 0; i < N; i++) {
@@ -85,6 +87,7 @@ static void run_combine(bool mont, u64 p, u64 g, u64 w) {
             want[i] = ref_point(p, w, col, r_mul(shift, r_pow(wn, i, p), p), ys, zs, alpha);
           }
           // the combine kernel's lanes: four points at stride N / 4
+          census_stage("deep_combine");
           for (u64 i = 0; i < q; i++) {
             E2 out[4];
             deep_combine_lane<F, K, 4>(x, D.dm, T, C, i, [&](u32 c, int t) { return M[c * N + i + (u64)t * q]; }, out);
@@ -93,6 +96,7 @@ static void run_combine(bool mont, u64 p, u64 g, u64 w) {
                     (unsigned long long)shift, variant, (unsigned long long)i, t);
           }
           // the check kernel's lanes: one point, from a gathered leaf
+          census_stage("deep_check");
           for (u64 i = 0; i < N; i += (n == 6 ? 5 : 1)) {
             E2 out[1];
             deep_combine_lane<F, K, 1>(x, D.dm, T, C, i, [&](u32 c, int) { return M[c * N + i]; }, out);
@@ -110,6 +114,7 @@ static void run_eval(bool mont, u64 p, u64 w) {
   const Ext2<F> x(f, ext2_reg_form(mont, p, w));
   const u64 ds[] = {1, 2, 255, 256, 257, 700};
   const u32 Ks[] = {1, 3, 8};
+  census_stage("deep_eval");
   for (u64 d : ds)
     for (u32 K : Ks) {
       std::vector<u64> coef(d);
@@ -146,9 +151,12 @@ int main(int argc, char** argv) {
   g_rng = p ^ g ^ w ^ 3;
   int policies = 0;
   if (p == gl64::P) {
+    census_policy("gl.");
     run_all_deep<FriGl>(false, p, g, w); policies |= 1;
+    census_policy("w7.");
     if (w % p == 7) { run_all_deep<FriGlW7>(false, p, g, w); policies |= 2; }
   }
+  census_policy("mont.");
   run_all_deep<FriMont>(true, p, g, w); policies |= 4;
   if (g_fail) { printf("FAILED %d checks\n", g_fail); return 1; }
   printf("OK p=%llu g=%llu w=%llu policies=%d\n", (unsigned long long)p, (unsigned long long)g, (unsigned long long)w, policies);

@@ -5,6 +5,11 @@
 //
 //   emu_ext2 <p> <g>     last line "OK ..." on success.  Goldilocks with g = 7 runs the shift policy, its W = 7 form (shift_policy=2)
 //                        AND the Montgomery policy.
+//
+// RONK_EMU_INPUT=<file> (Goldilocks only) is the file mode of the folds: little-endian words, case after case, each
+//   form (0 base, 1 base layer with an extension challenge, 2 planar pairs), eta, n, shift, beta0, beta1, then layer 0: 2^n words
+//   (2^(n+1) for form 2).  Every case goes through the fold bodies of the Goldilocks policy (and of its W = 7 form) and is compared
+//   with the restatement; nothing else runs.  tests/gl_directed.py fold_case writes such inputs.
 #define main emu_fri_main
 #include "emu_fri.cpp"
 #undef main
@@ -56,22 +61,33 @@ static void run_arith(bool mont, u64 p, u64 g) {
     if (it == 0) a = R2{0, 0};
     if (it == 1) a = R2{p - 1, p - 1};
     if (it == 2) a = R2{p, p + 1};   // zero and one as words >= p
+    if (emu_small() && it % 4 == 3) a.c0 = r_mul((u64)1 << 48, a.c0, p);   // (2^48)^2 = -1: a0^2 + W a1^2 is a small DIFFERENCE
     const u64 s = edge_word(p);
     const R2 ar = red(a, p), br = red(b, p);
+    census_stage("ext2_add");
     CHECK(out(x.add(in(a), in(b))) == x_add(ar, br, p), "add %d", it);
+    census_stage("ext2_sub");
     CHECK(out(x.sub(in(a), in(b))) == x_sub(ar, br, p), "sub %d", it);
+    census_stage("ext2_neg");
     CHECK(out(x.neg(in(a))) == x_sub(R2{0, 0}, ar, p), "neg %d", it);
+    census_stage("ext2_mul");
     CHECK(out(x.mul(in(a), in(b))) == x_mul(ar, br, w, p), "mul %d", it);
+    census_stage("ext2_sqr");
     CHECK(out(x.sqr(in(a))) == x_mul(ar, ar, w, p), "sqr %d", it);
+    census_stage("ext2_mul_base");
     CHECK(out(x.mul_base(in(a), f.in(s))) == x_scale(ar, s % p, p), "mul_base %d", it);
+    census_stage("ext2_norm");
     CHECK(f.out(x.norm(in(a))) == x_mul(ar, R2{ar.c0, r_sub(0, ar.c1, p)}, w, p).c0, "norm %d", it);
+    census_stage("ext2_inv");
     const R2 ai = out(x.inv(in(a)));
     CHECK(ai == x_inv(ar, w, p), "inv %d", it);
     if (ar.c0 | ar.c1) CHECK((x_mul(ai, ar, w, p) == R2{1, 0}), "a * a^-1 %d", it);
     else CHECK((ai == R2{0, 0}), "the inverse of zero is written as zero");
+    census_stage("ext2_pow");
     if (it < 40)
       for (u64 e : exps) CHECK(out(x.pow(in(a), e)) == x_pow(ar, e, w, p), "pow %d e=%llu", it, (unsigned long long)e);
   }
+  census_stage(nullptr);
   // Frobenius: a^p = (a0, -a1)
   const R2 a{rnd() % p, rnd() % p};
   CHECK((out(x.pow(in(a), p)) == R2{a.c0, r_sub(0, a.c1, p)}), "frobenius");
@@ -86,6 +102,8 @@ static void run_fold_ext(bool mont, u64 p, u64 g) {
   const u64 w = g % p;
   const u32 ns[] = {ETA, ETA + 1, 5 + ETA, 9};
   const u64 shifts[] = {1, g, p - 1};
+  static const char* const stage[2][4] = {{"", "fold_mix_eta1", "fold_mix_eta2", "fold_mix_eta3"}, {"", "fold_ext_eta1", "fold_ext_eta2", "fold_ext_eta3"}};
+  census_stage(stage[EXT_IN][ETA]);
   for (u32 n : ns)
     for (u64 shift : shifts) {
       Tables T;
@@ -115,11 +133,68 @@ static void run_fold_ext(bool mont, u64 p, u64 g) {
     }
 }
 
+// one case of the file mode
+template <class F, int ETA>
+static void run_fold_file(u64 p, u64 g, u32 form, u32 n, u64 shift, R2 beta, const std::vector<u64>& in) {
+  static const char* const stage[3][4] = {{"", "fold_base_eta1", "fold_base_eta2", "fold_base_eta3"},
+                                          {"", "fold_mix_eta1", "fold_mix_eta2", "fold_mix_eta3"},
+                                          {"", "fold_ext_eta1", "fold_ext_eta2", "fold_ext_eta3"}};
+  const u64 w = g % p;
+  Tables T;
+  make_tables(T, false, p, g, shift, n, ETA, n % ETA, 1, form ? 2 : 1);
+  const F f(T.k);
+  const u64 N = T.sh.size(0), m = N >> ETA;
+  if (form == 0) {
+    const std::vector<u64> want = ref_fold(p, g, in, beta.c0, shift % p, ETA);
+    census_stage(stage[0][ETA]);
+    for (u64 i = 0; i < m; i++) {
+      const u64 got = fri_fold_leaf<F, ETA>(f, fri_gamma(f, T.layers[0], i, f.in(beta.c0)), [&](int t) { return in[i + (u64)t * m]; });
+      CHECK(got == want[i], "file fold eta=%d n=%u i=%llu", ETA, n, (unsigned long long)i);
+    }
+  } else {
+    const Ext2<F> x(f, ext2_reg_form(false, p, w));
+    std::vector<R2> fin(N);
+    for (u64 i = 0; i < N; i++) fin[i] = R2{in[i], form == 2 ? in[N + i] : 0};
+    const std::vector<R2> want = x_fold(p, g, w, fin, beta, shift % p, ETA);
+    const E2 b{f.in(beta.c0), f.in(beta.c1)};
+    census_stage(stage[form][ETA]);
+    for (u64 i = 0; i < m; i++) {
+      const E2 gm = fri_gamma_ext(x, T.layers[0], i, b);
+      const E2 got = form == 2 ? fri_fold_leaf_ext<F, ETA, true>(x, gm, [&](int t) { return in[i + (u64)t * m]; })
+                               : fri_fold_leaf_ext<F, ETA, false>(x, gm, [&](int t) { return in[i + (u64)t * m]; });
+      CHECK(got.c0 == want[i].c0 && got.c1 == want[i].c1, "file fold form=%u eta=%d n=%u i=%llu", form, ETA, n, (unsigned long long)i);
+    }
+  }
+  census_stage(nullptr);
+}
+template <class F>
+static bool run_fold_cases(u64 p, u64 g, const std::vector<u64>& file, bool with_base, int* cases) {   // (the base form has no product with W)
+  size_t at = 0;
+  while (at < file.size()) {
+    if (file.size() - at < 6) return false;
+    const u64 form = file[at], eta = file[at + 1], n = file[at + 2], shift = file[at + 3];
+    const R2 beta{file[at + 4], file[at + 5]};
+    at += 6;
+    if (form > 2 || eta < 1 || eta > 3 || n < eta || n > 9 || shift % p == 0) return false;
+    const size_t len = (size_t)(form == 2 ? 2 : 1) << n;
+    if (file.size() - at < len) return false;
+    const std::vector<u64> in(file.begin() + at, file.begin() + at + len);
+    at += len;
+    if (form == 0 && !with_base) continue;
+    if (eta == 1) run_fold_file<F, 1>(p, g, (u32)form, (u32)n, shift, beta, in);
+    if (eta == 2) run_fold_file<F, 2>(p, g, (u32)form, (u32)n, shift, beta, in);
+    if (eta == 3) run_fold_file<F, 3>(p, g, (u32)form, (u32)n, shift, beta, in);
+    ++*cases;
+  }
+  return true;
+}
+
 // ---------------------------------------------------------------------------------------------------- transcript and verifier
 template <class F, int ETA, class PF, int W>
 static void run_proof_ext(bool mont, u64 p, u64 g, const Setup2& S, u32 in_ext) {
   const u32 n = 2 * ETA + 2, log2_final = 2, log2_blowup = 1;
   const u64 Q = 6, D = 2, A = (u64)1 << ETA, shift = g, w = g % p;
+  census_stage(nullptr);   // a composition of the bodies counted on their own
   Tables T;
   make_tables(T, mont, p, g, shift, n, ETA, log2_final, Q, D);
   T.sh.ext = 1; T.sh.in_ext = in_ext;
@@ -253,14 +328,35 @@ int main(int argc, char** argv) {
   const u64 p = strtoull(argv[1], nullptr, 0), g = strtoull(argv[2], nullptr, 0);
   if (!(p & 1) || ((p - 1) & 511)) { fprintf(stderr, "p - 1 must be a multiple of 2^9\n"); return 2; }
   g_rng = p ^ g ^ 2;
+  if (const char* path = getenv("RONK_EMU_INPUT")) {
+    bool ok = p == gl64::P;
+    for (u32 eta = 1; eta <= 3; eta++) ok = ok && fri_gl_shift_roots(p, g, eta);
+    std::vector<u64> file;
+    FILE* fp = ok ? fopen(path, "rb") : nullptr;
+    u64 word;
+    while (fp && fread(&word, 8, 1, fp) == 1) file.push_back(word);
+    if (fp) fclose(fp);
+    int cases = 0;
+    census_policy("gl.");
+    ok = fp && run_fold_cases<FriGl>(p, g, file, true, &cases);
+    census_policy("w7.");
+    if (ok && g % p == 7) ok = run_fold_cases<FriGlW7>(p, g, file, false, &cases);
+    if (!ok) { fprintf(stderr, "the file mode needs Goldilocks, a generator with shift roots and a well-formed %s\n", path); return 2; }
+    if (g_fail) { printf("FAILED %d checks\n", g_fail); return 1; }
+    printf("OK p=%llu g=%llu fold cases from the file: %d\n", (unsigned long long)p, (unsigned long long)g, cases);
+    return 0;
+  }
   Setup2 S;
   make_poseidon(S, p);
   int shift_policy = 0;
   if (p == gl64::P) {
     bool ok = true;
     for (u32 eta = 1; eta <= 3; eta++) ok = ok && fri_gl_shift_roots(p, g, eta);
+    census_policy("gl.");
     if (ok) { run_all_ext<FriGl, PosGl, 8>(false, p, g, S); shift_policy = 1; }
+    census_policy("w7.");
     if (ok && g % p == 7) { run_all_ext<FriGlW7, PosGl, 8>(false, p, g, S); shift_policy = 2; }   // W = g = 7: the shift form of the product with W
+    census_policy("mont.");
     run_all_ext<FriMont, PosGl, 8>(true, p, g, S);
   } else {
     run_all_ext<FriMont, PosMont, 8>(true, p, g, S);

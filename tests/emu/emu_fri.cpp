@@ -7,6 +7,7 @@
 #include "emu_poseidon.cpp"
 
 #include "../../ronkathon_amd/csrc/fri_kernels.h"
+#include "emu_census.h"
 using namespace ronk;
 
 
@@ -59,6 +60,8 @@ template <class F, int ETA>
 static void run_fold(bool mont, u64 p, u64 g) {
   const u32 ns[] = {ETA, ETA + 1, 5 + ETA, 9};
   const u64 shifts[] = {1, g, p - 1, rnd() % (p - 1) + 1};
+  static const char* const stage[] = {"", "fold_base_eta1", "fold_base_eta2", "fold_base_eta3"};
+  census_stage(stage[ETA]);
   for (u32 n : ns)
     for (u64 shift : shifts) {
       // every layer of a chain down to one word
@@ -113,6 +116,7 @@ template <class F, int ETA, class PF, int W>
 static void run_proof(bool mont, u64 p, u64 g, const Setup2& S) {
   const u32 n = 2 * ETA + 2, log2_final = 2, log2_blowup = 1;
   const u64 Q = 6, D = 2, A = (u64)1 << ETA, shift = g;
+  census_stage(nullptr);   // a composition of the bodies counted on their own
   Tables T;
   make_tables(T, mont, p, g, shift, n, ETA, log2_final, Q, D);
   const FriShape& sh = T.sh;
@@ -239,7 +243,9 @@ int main(int argc, char** argv) {
   if (p == gl64::P) {
     bool ok = true;
     for (u32 eta = 1; eta <= 3; eta++) ok = ok && fri_gl_shift_roots(p, g, eta);
+    census_policy("gl.");
     if (ok) { run_all<FriGl, PosGl, 8>(false, p, g, S); shift_policy = 1; }
+    census_policy("mont.");
     run_all<FriMont, PosGl, 8>(true, p, g, S);
   } else {
     run_all<FriMont, PosMont, 8>(true, p, g, S);

@@ -60,7 +60,7 @@ static void make_domain(Domain& D, bool mont, u64 p, u64 g, u64 shift, u32 n) {
   D.dm.lo = D.tab.data(); D.dm.hi = D.tab.data() + ((size_t)1 << kb); D.dm.kbits = kb; D.dm.log2n = n;
 }
 
-static u64 pair_word(u64 p, int c) { return c == 0 ? 0 : c == 1 ? 1 : c == 2 ? p - 1 : c == 3 ? p + 1 + rnd() % 3 : rnd() % p; }
+static u64 pair_word(u64 p, int c) { return c == 0 ? 0 : c == 1 ? 1 : c == 2 ? p - 1 : c == 3 ? p + 1 + rnd() % 3 : challenge_word(p); }
 
 template <class F, int K>
 static void run_shape(bool mont, u64 p, u64 g, u64 w, const Shape& s) {
@@ -100,9 +100,11 @@ static void run_shape(bool mont, u64 p, u64 g, u64 w, const Shape& s) {
         u64* tab_ap = tab_y + 2 * (size_t)R * K;
         const E2 a{f.in(aw[0]), f.in(aw[1])};
         int bits = 0;
+        census_stage("mpcs_prep");
         for (u32 c = 0; c < sh.Ctot; c++) deep_prep_column(x, a, c, tab_ap);
         for (u32 j = 0; j < (u32)K; j++) bits |= mpcs_prep_point(x, D.dm, a, zw.data(), sh, j, tab.data() + (size_t)MPCS_KW * j);
         for (u32 j = 0; j < R * (u32)K; j++) mpcs_prep_claims(x, a, yw.data(), sh, j / K, j % K, tab_y + 2 * (size_t)j);
+        census_stage(nullptr);
         CHECK(bits == (want_on ? 32 : 0), "status K=%d R=%u n=%u variant=%d bits=%d", K, R, n, variant, bits);
         for (u64 v : tab) CHECK(v != ~(u64)0 || p == ~(u64)0, "a table word is left unwritten K=%d R=%u", K, R);
         const MpcsTab T{tab.data(), tab_y, tab_ap};
@@ -115,6 +117,7 @@ static void run_shape(bool mont, u64 p, u64 g, u64 w, const Shape& s) {
           want[i] = ref_point(p, w, s, col, r_mul(shift, r_pow(wn, i, p), p), ys, zs, alpha);
         }
         // the combine kernel's lanes: four points at stride N / 4
+        census_stage("mpcs_combine");
         for (u64 i = 0; i < q; i++) {
           E2 out[4];
           mpcs_combine_lane<F, K, 4>(x, D.dm, T, sh, i, [&](u32 r, u32 c, int t) { return M[r][c * N + i + (u64)t * q]; }, out);
@@ -123,6 +126,7 @@ static void run_shape(bool mont, u64 p, u64 g, u64 w, const Shape& s) {
                   (unsigned long long)shift, variant, (unsigned long long)i, t);
         }
         // the check kernel's lanes: one point, from the gathered leaves
+        census_stage("mpcs_check");
         for (u64 i = 0; i < N; i += (n == 6 ? 5 : 1)) {
           E2 out[1];
           mpcs_combine_lane<F, K, 1>(x, D.dm, T, sh, i, [&](u32 r, u32 c, int) { return M[r][c * N + i]; }, out);
@@ -155,9 +159,12 @@ int main(int argc, char** argv) {
   g_rng = p ^ g ^ w ^ 5;
   int policies = 0;
   if (p == gl64::P) {
+    census_policy("gl.");
     run_all_mpcs<FriGl>(false, p, g, w); policies |= 1;
+    census_policy("w7.");
     if (w % p == 7) { run_all_mpcs<FriGlW7>(false, p, g, w); policies |= 2; }
   }
+  census_policy("mont.");
   run_all_mpcs<FriMont>(true, p, g, w); policies |= 4;
   // what the host shape refuses
   {

@@ -20,6 +20,7 @@
 #include "../../ronkathon_amd/csrc/plonk_kernels.h"
 using namespace ronk;
 #include "emu_ref.h"
+#include "emu_census.h"
 
 // ---------------------------------------------------------------------------------------------------- the restatement
 struct Shape {
@@ -82,6 +83,7 @@ static std::vector<u64> emu_quotient(bool mont, const Shape& s, const Inputs& in
   const PlonkCols cols{in.wires.data(), in.sel.data(), in.sigma.data(), in.with_pi ? in.pi.data() : nullptr, in.Z.data(),
                        in.alpha, in.beta, in.gamma};
   std::vector<u64> T(2 * M, ~(u64)0);
+  census_stage("plonk");
   auto run = [&](auto PP) {
     constexpr int PTS = decltype(PP)::value;
     const u64 q = M / PTS, grid = (q + PLONK_LANES - 1) / PLONK_LANES;
@@ -98,6 +100,7 @@ static std::vector<u64> emu_quotient(bool mont, const Shape& s, const Inputs& in
   };
   if (log2m < PlonkRows<F>::LOG2) run(std::integral_constant<int, 1>{});
   else run(std::integral_constant<int, 1 << PlonkRows<F>::LOG2>{});
+  census_stage(nullptr);
   return T;
 }
 
@@ -135,15 +138,18 @@ int main(int argc, char** argv) {
     in.wires.resize(3 * M); in.sel.resize(5 * M); in.sigma.resize(3 * M); in.pi.resize(M); in.Z.resize(2 * M);
     for (auto* v : {&in.wires, &in.sel, &in.sigma, &in.pi, &in.Z})
       for (auto& t : *v) t = edge_word(p);
-    for (int j = 0; j < 2; j++) { in.alpha[j] = edge_word(p); in.beta[j] = rnd(); in.gamma[j] = rnd(); }
+    for (int j = 0; j < 2; j++) { in.alpha[j] = edge_word(p); in.beta[j] = emu_small() ? edge_word(p) : rnd(); in.gamma[j] = emu_small() ? edge_word(p) : rnd(); }   // (the directed mode of emu_ref.h: small challenges too)
   }
   const Inputs before = in;
   std::vector<std::vector<u64>> results;
   int policies = 0;
   if (p == gl64::P) {
+    census_policy("gl.");
     results.push_back(emu_quotient<FriGl>(false, s, in)); policies |= 1;
+    census_policy("w7.");
     if (s.w % p == 7) { results.push_back(emu_quotient<FriGlW7>(false, s, in)); policies |= 2; }
   }
+  census_policy("mont.");
   results.push_back(emu_quotient<FriMont>(true, s, in)); policies |= 4;
   CHECK(before.wires == in.wires && before.sel == in.sel && before.sigma == in.sigma && before.Z == in.Z, "an input changed");
   // every row at the small sizes, else the ends, the stride boundaries and a sample

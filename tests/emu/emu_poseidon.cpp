@@ -4,6 +4,12 @@
 //
 //   emu_poseidon <p> <width> <alpha> <num_p> <num_f> <rate> <seed>     last line "OK ..." on success
 //
+// RONK_EMU_INPUT=<file> is the file mode (tests/gl_directed.py poseidon_blob: little-endian words n_states, n_words, rc, mds,
+// the states, the words): the constants and the permutation states come from the file, the sponge and leaf inputs are drawn from
+// its words in turn, and every output is still compared with the restatement.  RONK_EMU_SMALL=B (emu_ref.h) is the directed
+// mode of the emulator's own generator: round constants, states and absorbed words in [-B, B], a matrix of two +-1 per row.
+// -DRONK_GL64_CENSUS: emu_census.h.
+//
 // Built with -DEMU_POSEIDON_LIB -shared, the restatement alone is a small library (posref_*) that tests/test_gpu_poseidon.py
 // uses for trees too large for the Python restatement (which pins it on small ones).  -fopenmp spreads the tree over threads.
 #include <stdint.h>
@@ -105,7 +111,16 @@ void posref_merkle(u64 p, u32 width, u64 alpha, u32 num_p, u32 num_f, u32 rate, 
 #ifndef EMU_POSEIDON_LIB
 // ---------------------------------------------------------------------------------------------------- the kernel bodies
 #include "../../ronkathon_amd/csrc/poseidon_kernels.h"
+#include "emu_census.h"
 using namespace ronk;
+
+// file mode: the states of the permutation check, and the words the other inputs are drawn from
+static std::vector<u64> g_file_states, g_file_words;
+static size_t g_file_next = 0;
+static bool file_mode() { return !g_file_words.empty(); }
+static u64 file_word() { const u64 v = g_file_words[g_file_next]; g_file_next = (g_file_next + 1) % g_file_words.size(); return v; }
+static bool directed() { return file_mode() || emu_small(); }
+static u64 directed_word(u64 p) { return file_mode() ? file_word() : small_word(p, emu_small()); }
 
 static bool g_negatives = true;   // off for the all-equal matrix: its hash only sees the SUM of what it absorbs
 
@@ -143,6 +158,7 @@ static void run_w(const Setup& S, u64 seed) {
   // ---- permutation: edge states and random ones, inputs >= p included
   {
     const F f(S.nat);
+    census_stage("permute");
     std::vector<std::vector<u64>> states;
     states.push_back(std::vector<u64>(width, 0));
     states.push_back(std::vector<u64>(width, p - 1));
@@ -152,6 +168,14 @@ static void run_w(const Setup& S, u64 seed) {
       std::vector<u64> s(width);
       for (auto& v : s) { const u64 c = rnd() % 8; v = c == 0 ? p - 1 : c == 1 ? 0 : c == 2 ? p + rnd() % 5 : rnd(); }
       states.push_back(s);
+    }
+    if (file_mode()) {
+      states.clear();
+      for (size_t i = 0; i + width <= g_file_states.size(); i += width) states.emplace_back(g_file_states.begin() + i, g_file_states.begin() + i + width);
+    } else if (emu_small()) {
+      states.assign(200, std::vector<u64>(width));
+      for (auto& s : states)
+        for (auto& v : s) v = small_word(p, emu_small());
     }
     for (auto& s : states) {
       std::vector<u64> want(s), got(s);
@@ -169,6 +193,8 @@ static void run_w(const Setup& S, u64 seed) {
     const size_t items = 5, maxlen = 3 * (size_t)rate + 2;
     std::vector<u64> mat(items * maxlen);
     for (auto& v : mat) { const u64 c = rnd() % 8; v = c == 0 ? p - 1 : c == 1 ? 0 : c == 2 ? p + rnd() % 5 : rnd(); }
+    if (directed()) for (auto& v : mat) v = directed_word(p);
+    census_stage("sponge");
     for (size_t len : lens)
       for (size_t n_out : nouts)
         for (int layout = 0; layout < 2; layout++) {
@@ -191,6 +217,7 @@ static void run_w(const Setup& S, u64 seed) {
       const size_t leaf_len = 1 + seed % 5;
       std::vector<u64> leaves(n * leaf_len);
       for (auto& v : leaves) v = rnd();
+      if (directed()) for (auto& v : leaves) v = directed_word(p);
       const size_t words = ref_tree_words(n, d);
       CHECK(words == merkle_level_offset(n, d, merkle_levels(n)), "tree words n=%zu", n);
       std::vector<u64> want(words), tree(words, ~(u64)0);
@@ -199,12 +226,14 @@ static void run_w(const Setup& S, u64 seed) {
       const u64 top = merkle_levels(n) - 1;
       std::vector<u64> bufa(MERKLE_BLOCK * d), bufb(MERKLE_BLOCK / 2 * d);
       auto lanes = [&](auto&& fn) { for (u32 t = 0; t < MERKLE_BLOCK; t++) fn(t); };
+      census_stage("merkle_leaf");
       for (u64 i = 0; i < n; i++) {
         const u64* src = leaves.data() + i * leaf_len;
         u64* g = tree.data() + i * d;
         poseidon_sponge<F, W>(f, S.sp, leaf_len, d, [&](u64 j) { return src[j]; }, [&](u64 q, u64 v) { g[q] = v; });
       }
       u64 lvl = 0, n_lvl = n, off = 0;
+      census_stage("merkle_node");
       while (n_lvl > MERKLE_BLOCK) {
         const u64 cn = (n_lvl + 1) / 2;
         for (u64 t = 0; t < cn; t++) merkle_level_node<F, W>(f, S.sp, tree.data() + off, n_lvl, d, tree.data() + off + n_lvl * d, t);
@@ -216,6 +245,7 @@ static void run_w(const Setup& S, u64 seed) {
         merkle_climb<F, W>(f, S.sp, bufa.data(), bufb.data(), 0, cnt, d, (u32)(top - lvl), n_lvl, off + n_lvl * d, tree.data(), lanes);
       }
       CHECK(want == tree, "merkle tree n=%zu", n);
+      census_stage("merkle_verify");
       // open + verify every index
       const u64 depth = top;
       std::vector<u64> path(depth * d + 1), h(3 * d);
@@ -278,11 +308,33 @@ int main(int argc, char** argv) {
   std::vector<u64> rc((size_t)rounds * width), mds((size_t)width * width);
   for (auto& c : rc) c = rnd();
   for (auto& c : mds) c = rnd();
+  if (const char* path = getenv("RONK_EMU_INPUT")) {
+    FILE* fp = fopen(path, "rb");
+    u64 head[2] = {0, 0};
+    bool ok = fp && fread(head, 8, 2, fp) == 2 && head[0] < (1u << 20) && head[1] >= 1 && head[1] < (1u << 24);
+    if (ok) {
+      g_file_states.resize(head[0] * width);
+      g_file_words.resize(head[1]);
+      ok = fread(rc.data(), 8, rc.size(), fp) == rc.size() && fread(mds.data(), 8, mds.size(), fp) == mds.size() &&
+           fread(g_file_states.data(), 8, g_file_states.size(), fp) == g_file_states.size() &&
+           fread(g_file_words.data(), 8, g_file_words.size(), fp) == g_file_words.size() && fgetc(fp) == EOF;
+    }
+    if (fp) fclose(fp);
+    if (!ok) { fprintf(stderr, "cannot read %s for width %u and %u rounds\n", path, width, rounds); return 2; }
+  } else if (emu_small()) {
+    for (auto& c : rc) c = small_word(p, emu_small());
+    for (u32 i = 0; i < width; i++) {
+      const u32 a = (u32)(rnd() % width), b = (a + 1 + (u32)(rnd() % (width - 1))) % width;
+      for (u32 j = 0; j < width; j++) mds[(size_t)i * width + j] = j == a || j == b ? (rnd() & 1 ? 1 : p - 1) : 0;
+    }
+  }
+  if (directed()) g_negatives = false;   // small constants are no hash: equal digests of different leaves are common
   make_setup(S, p, width, alpha, num_p, num_f, rate, rc, mds);
   run(S, seed);
+  census_stage(nullptr);
   // the accumulator's worst case: every state word and every matrix entry p - 1, round constants zero; a row is then
-  // width * (p - 1)^2 before its one reduction
-  {
+  // width * (p - 1)^2 before its one reduction (not in the directed modes: those runs are about their own inputs)
+  if (!directed()) {
     std::vector<u64> rc0((size_t)rounds * width, 0), m1((size_t)width * width, p - 1);
     Setup T;
     make_setup(T, p, width, alpha, num_p, num_f, rate, rc0, m1);

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 typedef uint64_t u64;
 typedef unsigned __int128 u128;
@@ -27,11 +28,23 @@ static inline u64 r_pow(u64 a, u64 e, u64 p) {
   while (e) { if (e & 1) r = r_mul(r, a, p); a = r_mul(a, a, p); e >>= 1; }
   return r;
 }
+// The directed mode (tests/test_emu_gl_directed.py): with RONK_EMU_SMALL=B in the environment every input word is SMALL SIGNED,
+// t mod p for t uniform in [-B, B], and so is every challenge drawn through challenge_word; sums and products of such words
+// land in [p, 2^64) all the time, which uniform residues never do.  Unset, every draw is what it was.
+static inline u64 emu_small() {
+  static long b = -1;
+  if (b < 0) { const char* e = getenv("RONK_EMU_SMALL"); b = e ? atol(e) : 0; }
+  return (u64)b;
+}
+static inline u64 small_word(u64 p, u64 B) { const u64 r = rnd() % (2 * B + 1); return r <= B ? r : p - (r - B); }
 // an input word: p - 1, 0, a word just above p, or any word
 static inline u64 edge_word(u64 p) {
+  if (emu_small()) return small_word(p, emu_small());
   const u64 c = rnd() % 8;
   return c == 0 ? p - 1 : c == 1 ? 0 : c == 2 && p < ~(u64)0 - 5 ? p + rnd() % 5 : rnd();
 }
+// a challenge: any residue
+static inline u64 challenge_word(u64 p) { return emu_small() ? small_word(p, emu_small()) : rnd() % p; }
 
 // ---------------------------------------------------------------------------------------------------- the extension
 struct R2 { u64 c0, c1; };

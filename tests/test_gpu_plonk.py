@@ -48,15 +48,18 @@ def garbage(torch, n):
 
 
 class Case:
-    """random words for one (field, M, B), on the host and on the device"""
+    """random words for one (field, M, B), on the host and on the device; or the caller's `host` arrays in their place: wires 3M,
+    selectors 5M, sigma 3M, pi M, Z 2M, then alpha, beta, gamma of two words each"""
 
-    def __init__(self, torch, p, w, log2_m, log2_b, seed=0):
+    def __init__(self, torch, p, w, log2_m, log2_b, seed=0, host=None):
         self.p, self.w, self.M, self.log2_m, self.log2_b = p, w, 1 << log2_m, log2_m, log2_b
         M = self.M
         self.E = PR.Ext2(p, w)
         self.dom = PR.Domain(p, GEN[p], log2_m - log2_b, log2_b, GEN[p])
         s = 1000 * log2_m + 10 * log2_b + seed
-        self.host = [words(s + j, k * M, p) for j, k in enumerate((3, 5, 3, 1, 2))] + [words(s + 5 + j, 2, p) for j in range(3)]
+        self.host = host if host is not None else \
+            [words(s + j, k * M, p) for j, k in enumerate((3, 5, 3, 1, 2))] + [words(s + 5 + j, 2, p) for j in range(3)]
+        assert [a.size for a in self.host] == [3 * M, 5 * M, 3 * M, M, 2 * M, 2, 2, 2]
         self.dev = [dev(torch, a) for a in self.host]
         self.handle = Handle(p, GEN[p], w, log2_m - log2_b, log2_b, GEN[p])
         wires, sel, sigma, pi, Z = self.host[:5]
