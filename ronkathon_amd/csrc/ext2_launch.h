@@ -1,6 +1,6 @@
 // ext2_launch.h -- what a host-side launch of the field-policy family FriGl / FriGlW7 / FriMont (csrc/fri_kernels.h) knows, and the
 // two forms that bind FF to the policy.  Shared by ronk_ext2.hip, ronk_accum.hip, ronk_plonk.hip,
-// ronk_pcs.hip and ronk_fri.hip; not part of the C ABI.
+// ronk_mpcs.hip (and through it ronk_pcs.hip) and ronk_fri.hip; not part of the C ABI.
 #pragma once
 #include "runtime.h"
 #include "ext2_kernels.h"

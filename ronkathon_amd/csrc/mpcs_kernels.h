@@ -15,9 +15,12 @@
 //   3. adds B_k (d, z1) ninv (S_r - Y_r,k) for the points of the round's mask; B_k (d, z1) = B_k d + B_k (0, z1) is recomputed per
 //      round (two base products), which keeps K registers per point and not 3 K.
 // The masks and column counts are wave-uniform; K and PTS are compile-time, so every (t, k) array is indexed by constants.
-// For R = 1 with a full mask G is the codeword of deep_kernels.h, word for word (both are canonical).
+// R = 1 with the full mask (mpcs_full_mask) is the batched commitment of one matrix, ronk_pcs_* (csrc/ronk_pcs.hip; DESIGN.md
+// section 15): G[i] = sum_k B_k (S_i - Y_k) (x_i - z_k)^-1 with B_k = alpha^(k C).  The prover's lane of a one-round handle takes
+// the steps in another order, rows first (mpcs_one_round_lane); table, prep and check are the same.
 //
-// Plain C++ on uint64, so tests/emu/emu_mpcs.cpp compiles the same bodies for the host.
+// Plain C++ on uint64, so tests/emu/emu_mpcs.cpp compiles the same bodies for the host, and tests/emu/emu_deep.cpp the one-round
+// case.
 #pragma once
 #include "deep_kernels.h"
 
@@ -44,6 +47,8 @@ RONK_HD u32 mpcs_popcount(u32 v) {
   for (; v; v &= v - 1) n++;
   return n;
 }
+// every one of K <= DEEP_MAX_K points: the mask of the one round of ronk_pcs_* and of ronk_ext2_poly_eval_batch*
+RONK_HD u32 mpcs_full_mask(u32 K) { return (1u << K) - 1; }
 // the claim y[r][k][c] is element yoff_r + rank_r(k) C_r + c of a plane; rank_r(k): the set bits of mask_r below k
 RONK_HD u32 mpcs_claim_index(const MpcsShape& sh, u32 r, u32 k, u32 c) {
   return sh.yoff[r] + mpcs_popcount(sh.mask[r] & ((1u << k) - 1)) * sh.C[r] + c;
@@ -160,6 +165,59 @@ RONK_HD void mpcs_combine_lane(const Ext2<F>& x, const DeepDomain& dm, const Mpc
       });
     });
   }
+  deep_for<0, PTS>([&](auto T) { constexpr int t = decltype(T)::value; out[t] = E2{f.out(G[t].c0), f.out(G[t].c1)}; });
+}
+
+// The prover's lane of a ONE-round handle (R = 1, hence the full mask; every ronk_pcs handle): the same words from the same table
+// in the order of the first combine kernel, S over the C rows FIRST, then the norms, the one inversion, and the quotients added
+// while Montgomery's trick unwinds (the prefix products are kept, a norm is recomputed on the way back).  With one round nothing is
+// held across rounds, and the loads of a lane are issued before its inversion chain: at K = 1 over Goldilocks the order above is
+// 6 to 9 % slower.  The check kernel has one body, mpcs_combine_lane<F, K, 1>, whatever R.
+template <class F, int K, class Load>
+RONK_HD void mpcs_one_round_lane(const Ext2<F>& x, const DeepDomain& dm, const MpcsTab& tab, u32 C, u64 i, Load&& load,
+                                 E2 (&out)[DEEP_PTS]) {
+  constexpr int PTS = DEEP_PTS;
+  const F& f = x.f;
+  E2 S[PTS];
+  deep_for<0, PTS>([&](auto T) { S[decltype(T)::value] = x.zero(); });
+  const FriTable ap = (FriTable)tab.ap;
+  for (u32 c = 0; c < C; c++) {
+    const u64 a0 = ap[2 * (u64)c], a1 = ap[2 * (u64)c + 1];
+    deep_for<0, PTS>([&](auto T) { constexpr int t = decltype(T)::value; S[t] = deep_accumulate(f, S[t], load(c, t), a0, a1); });
+  }
+  u64 xs[PTS];
+  xs[0] = deep_point(f, dm, i);
+  xs[1] = f.mul(xs[0], dm.iota);
+  xs[2] = f.neg(xs[0]);
+  xs[3] = f.neg(xs[1]);
+  // the records and the Y_k are few and wave-uniform: a local copy keeps them in scalar registers
+  u64 krec[K * MPCS_KW], yrec[2 * K];
+  const FriTable kr = (FriTable)tab.k, yt = (FriTable)tab.y;
+  deep_for<0, K * (int)MPCS_KW>([&](auto J) { krec[decltype(J)::value] = kr[decltype(J)::value]; });
+  deep_for<0, 2 * K>([&](auto J) { yrec[decltype(J)::value] = yt[decltype(J)::value]; });
+  u64 pre[PTS * K];
+  u64 run = f.one();
+  deep_for<0, PTS * K>([&](auto I) {
+    constexpr int t = decltype(I)::value / K, k = decltype(I)::value % K;
+    bool zero;
+    const u64 n = deep_norm(f, f.sub(xs[t], krec[k * MPCS_KW]), krec[k * MPCS_KW + 1], zero);
+    pre[t * K + k] = run;
+    run = f.mul(run, n);
+  });
+  u64 inv = deep_inverse(x, run);
+  E2 G[PTS];
+  deep_for<0, PTS>([&](auto T) { G[decltype(T)::value] = x.zero(); });
+  deep_for<0, PTS * K>([&](auto I) {
+    constexpr int J = PTS * K - 1 - decltype(I)::value, t = J / K, k = J % K, r = k * (int)MPCS_KW;
+    bool zero;
+    const u64 d = f.sub(xs[t], krec[r]);
+    const u64 n = deep_norm(f, d, krec[r + 1], zero);
+    u64 ninv = f.mul(inv, pre[J]);
+    inv = f.mul(inv, n);
+    if (zero) ninv = 0;
+    const E2 B{f.add(f.mul(krec[r + 2], d), krec[r + 4]), f.add(f.mul(krec[r + 3], d), krec[r + 5])};   // B_k (d, z1)
+    G[t] = x.add(G[t], x.mul_base(x.mul(x.sub(S[t], E2{yrec[2 * k], yrec[2 * k + 1]}), B), ninv));
+  });
   deep_for<0, PTS>([&](auto T) { constexpr int t = decltype(T)::value; out[t] = E2{f.out(G[t].c0), f.out(G[t].c1)}; });
 }
 

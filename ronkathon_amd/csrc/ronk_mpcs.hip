@@ -3,6 +3,9 @@
 // extension points, combined into one DEEP codeword and opened under one FRI.  The Merkle tree, the openings, the extension FRI
 // prover and verifier are the merged ones, used through their own entry points; the evaluation body, the domain table and the
 // inversion are those of csrc/deep_kernels.h.  The R device pointers of a call travel to the kernels by value (MpcsPtrs).
+// The batched commitment of one matrix, ronk_pcs_* (csrc/ronk_pcs.hip), is this code with R = 1 and the full mask (the combine
+// launch of a one-round handle walks the rows before it inverts, mpcs_one_round_kernel; everything else is shared), and
+// ronk_ext2_poly_eval_batch* (include/ronk_ntt.h "batched FRI polynomial commitment") is the evaluation kernel on its own.
 #include "runtime.h"
 #include "hip_launch.h"
 #include "poseidon_handle.h"
@@ -60,8 +63,8 @@ struct ronk_mpcs {
 #define MPCS_DISPATCH(h, ...) EXT2_DISPATCH3((h)->c, MPCS_DISPATCH_K((h)->ms.K, __VA_ARGS__))
 
 // ------------------------------------------------------------------------------------- kernels
-// One workgroup per column of one round, the body of the batched commitment's evaluation kernel: slot j of the lane is the j-th
-// point of the round's mask.  y0, y1: the round's claims in the two planes, element j C + c.
+// One workgroup per column of one round: lane l takes the coefficients l + 256 r, the shares meet in an LDS tree.  Slot j of the
+// lane is the j-th point of the round's mask.  y0, y1: the round's claims in the two planes, element j C + c.
 template <class F>
 __global__ void __launch_bounds__(DEEP_EVAL_LANES) mpcs_eval_kernel(FriConsts k, u64 w, const u64* __restrict__ coef, u64 d,
                                                                     const u64* __restrict__ z, u32 K, u32 mask, u32 C,
@@ -154,6 +157,24 @@ __global__ void __launch_bounds__(256) mpcs_combine_kernel(FriConsts k, u64 w, D
   if (i >= q) return;
   E2 out[DEEP_PTS];
   mpcs_combine_lane<F, K, DEEP_PTS>(x, dm, tab, sh, i, [&](u32 r, u32 c, int t) { return M.p[r][(u64)c * N + i + (u64)t * q]; }, out);
+  deep_for<0, DEEP_PTS>([&](auto T) {
+    constexpr int t = decltype(T)::value;
+    G[i + (u64)t * q] = out[t].c0;
+    G[N + i + (u64)t * q] = out[t].c1;
+  });
+}
+
+// the same grid for a handle of ONE round: the lane that walks the rows first (mpcs_one_round_lane), the same words
+template <class F, int K>
+__global__ void __launch_bounds__(256) mpcs_one_round_kernel(FriConsts k, u64 w, DeepDomain dm, MpcsTab tab, u32 C,
+                                                             const u64* __restrict__ M, u64* __restrict__ G) {
+  const F f(k);
+  const Ext2<F> x(f, w);
+  const u64 N = (u64)1 << dm.log2n, q = N >> 2;
+  const u64 i = blockIdx.x * (u64)blockDim.x + threadIdx.x;
+  if (i >= q) return;
+  E2 out[DEEP_PTS];
+  mpcs_one_round_lane<F, K>(x, dm, tab, C, i, [&](u32 c, int t) { return M[(u64)c * N + i + (u64)t * q]; }, out);
   deep_for<0, DEEP_PTS>([&](auto T) {
     constexpr int t = decltype(T)::value;
     G[i + (u64)t * q] = out[t].c0;
@@ -290,6 +311,26 @@ extern "C" size_t ronk_mpcs_handle_proof_words(const ronk_mpcs* h) { return h ? 
 extern "C" size_t ronk_mpcs_handle_workspace_words(const ronk_mpcs* h) { return h ? (size_t)h->workspace_words() : 0; }
 
 // ------------------------------------------------------------------------------------- device entry points
+// C columns of d coefficients at the points of mask; y0, y1: the two planes of the claims
+static int mpcs_eval_launch(const Ext2Launch& c, const u64* d_coef, u32 C, u64 d, const u64* d_z, u32 K, u32 mask, u64* d_y0, u64* d_y1,
+                            hipStream_t s) {
+  EXT2_DISPATCH3(c, hipLaunchKernelGGL((mpcs_eval_kernel<FF>), dim3(C), dim3(DEEP_EVAL_LANES), 0, s, c.k, c.w, d_coef, d, d_z, K, mask, C,
+                                       d_y0, d_y1));
+  HIPCHK(hipGetLastError());
+  return RONK_OK;
+}
+
+// no handle, any odd prime: every column at every point, y planar [2][K C]
+extern "C" int ronk_ext2_poly_eval_batch_dev(uint64_t p, uint64_t w, const uint64_t* d_coef, uint32_t n_columns, size_t d,
+                                             const uint64_t* d_z, uint32_t n_points, uint64_t* d_y, void* stream) {
+  if (!d_coef || !d_z || !d_y || !n_columns || !n_points || !d) return RONK_ERR_INVALID;
+  RCHK(ronk_ext2_check(p, w));
+  if (n_points > DEEP_MAX_K || n_columns > (1u << 24)) return RONK_ERR_UNSUPPORTED;
+  RCHK(need_device());
+  return mpcs_eval_launch(ext2_launch(p, w), d_coef, n_columns, d, d_z, n_points, mpcs_full_mask(n_points), d_y,
+                          d_y + (u64)n_points * n_columns, (hipStream_t)stream);
+}
+
 static bool mpcs_all(const ronk_mpcs* h, const uint64_t* const* a) {
   if (!a) return false;
   for (u32 r = 0; r < h->ms.R; r++)
@@ -327,9 +368,15 @@ extern "C" int ronk_mpcs_combine_dev(const ronk_mpcs* h, const uint64_t* const* 
   if ((q + 255) / 256 > 0x7fffffffull) return RONK_ERR_UNSUPPORTED;
   HIPCHK(hipMemsetAsync(d_status, 0, sizeof(int), s));
   RCHK(mpcs_prep_dev(h, d_alpha, d_z, d_y, d_status, s));
-  const MpcsPtrs M = mpcs_ptrs(h, d_M);
-  MPCS_DISPATCH(h, hipLaunchKernelGGL((mpcs_combine_kernel<FF, KK>), dim3((u32)((q + 255) / 256)), dim3(256), 0, s, h->c.k, h->c.w, h->dm,
-                                      h->tab(), h->ms, M, d_G));
+  const dim3 grid((u32)((q + 255) / 256));
+  if (h->ms.R == 1) {   // one round has the full mask (ronk_mpcs_check): rows first
+    MPCS_DISPATCH(h, hipLaunchKernelGGL((mpcs_one_round_kernel<FF, KK>), grid, dim3(256), 0, s, h->c.k, h->c.w, h->dm, h->tab(), h->ms.C[0],
+                                        d_M[0], d_G));
+  } else {
+    const MpcsPtrs M = mpcs_ptrs(h, d_M);
+    MPCS_DISPATCH(h, hipLaunchKernelGGL((mpcs_combine_kernel<FF, KK>), grid, dim3(256), 0, s, h->c.k, h->c.w, h->dm, h->tab(), h->ms, M,
+                                        d_G));
+  }
   HIPCHK(hipGetLastError());
   return RONK_OK;
 }
@@ -359,10 +406,8 @@ extern "C" int ronk_mpcs_open_dev(const ronk_mpcs* h, const uint64_t* const* d_M
   u64* d_round = d_fri_proof + h->fri_proof();
   MpcsPtrs roots{};
   for (u32 r = 0; r < ms.R; r++) {
-    EXT2_DISPATCH3(h->c, hipLaunchKernelGGL((mpcs_eval_kernel<FF>), dim3(ms.C[r]), dim3(DEEP_EVAL_LANES), 0, s, h->c.k, h->c.w, d_coef[r],
-                                                     N >> h->log2_blowup, d_z, ms.K, ms.mask[r], ms.C[r], d_claims + ms.yoff[r],
-                                                     d_claims + ms.Y + ms.yoff[r]));
-    HIPCHK(hipGetLastError());
+    RCHK(mpcs_eval_launch(h->c, d_coef[r], ms.C[r], N >> h->log2_blowup, d_z, ms.K, ms.mask[r], d_claims + ms.yoff[r],
+                          d_claims + ms.Y + ms.yoff[r], s));
     roots.p[r] = d_tree[r] + ronk_merkle_tree_words(m, D) - D;
   }
   RCHK(mpcs_transcript_dev(h, d_seed, roots, d_z, d_claims, d_a, s));
@@ -412,6 +457,21 @@ extern "C" int ronk_mpcs_verify_dev(const ronk_mpcs* h, const uint64_t* d_roots,
 }
 
 // ------------------------------------------------------------------------------------- host-pointer forms, synchronous
+extern "C" int ronk_ext2_poly_eval_batch(uint64_t p, uint64_t w, const uint64_t* coef, uint32_t n_columns, size_t d, const uint64_t* z,
+                                         uint32_t n_points, uint64_t* y) {
+  if (!coef || !z || !y || !n_columns || !n_points || !d) return RONK_ERR_INVALID;
+  RCHK(ronk_ext2_check(p, w));
+  if (n_points > DEEP_MAX_K || n_columns > (1u << 24)) return RONK_ERR_UNSUPPORTED;
+  RCHK(need_device());
+  const size_t ny = 2 * (size_t)n_points * n_columns;
+  HostCall hc;
+  const u64 *dc = hc.in(coef, (size_t)n_columns * d), *dz = hc.in(z, 2 * (size_t)n_points);
+  u64* dy = hc.out(ny);
+  RCHK(hc.rc);
+  RCHK(ronk_ext2_poly_eval_batch_dev(p, w, dc, n_columns, d, dz, n_points, dy, nullptr));
+  return hc.get(y, dy, ny * 8);
+}
+
 extern "C" int ronk_mpcs_commit(const ronk_mpcs* h, uint32_t round, const uint64_t* M, uint64_t* tree) {
   if (!h || round >= h->ms.R || !M || !tree) return RONK_ERR_INVALID;
   const size_t nt = ronk_merkle_tree_words((size_t)1 << h->sh.log2m(0), h->sh.d);

@@ -7,8 +7,8 @@
 //   ronk_dist.hip     multi-GPU four-step phases
 //   ronk_recover.hip  the product tree and erasure recovery;  ronk_multipoint.hip  multipoint evaluation / interpolation on it
 //   ronk_hash.hip     Poseidon and Merkle;  ronk_msm.hip  BN254 MSM and kzg::open;  ronk_fr_ntt.hip  the BN254 scalar-field NTT
-//   ronk_ext2.hip, ronk_accum.hip, ronk_plonk.hip, ronk_pcs.hip, ronk_fri.hip  the extension-field family: one launch context and
-//                     dispatch (ext2_launch.h)
+//   ronk_ext2.hip, ronk_accum.hip, ronk_plonk.hip, ronk_mpcs.hip, ronk_fri.hip  the extension-field family: one launch context and
+//                     dispatch (ext2_launch.h);  ronk_pcs.hip  the one-round view of ronk_mpcs.hip, through its entry points
 // Every host-pointer entry point is a HostCall (below) around its _dev twin.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -49,7 +49,7 @@ bool newton_field(const FieldCtx& f, size_t d, u64* g);
 int newton_ladder_dev(const FieldCtx& fld, u64 G, const u64* f, size_t Lp, u64* g, u64* e, u64* h, u64* t1, hipStream_t s);
 
 // ---- FRI (ronk_fri.hip): the device array in which the last ronk_fri_verify_dev or ronk_fri_query_indices_dev call on the handle
-//      left j_0 of every query, in stream order (ronk_pcs.hip reads it instead of replaying the transcript)
+//      left j_0 of every query, in stream order (ronk_mpcs.hip reads it instead of replaying the transcript)
 const u64* fri_handle_indices(const ronk_fri* h);
 
 // ---- proof of work (ronk_pow.hip), arguments already checked: the prefix and the search launch (d_work: ronk_pow_workspace_words

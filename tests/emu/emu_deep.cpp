@@ -1,7 +1,8 @@
-// emu_deep.cpp -- the bodies of csrc/deep_kernels.h (the table of a call, the DEEP combination of a lane's points for the combine
-// kernel's four points and the check kernel's one, the evaluation at extension points) compiled for the host and compared with a
-// plain `unsigned __int128 % p` restatement in this file: the double sum of the definition and Horner's rule, over the arithmetic
-// of emu_ref.h (which emu_fri.cpp brings in).  Test infrastructure only; never part of the product library.
+// emu_deep.cpp -- the bodies that ronk_pcs_* runs, compiled for the host: the one-round case of csrc/mpcs_kernels.h (one matrix of C
+// columns under mpcs_full_mask(K), the mapping of csrc/ronk_pcs.hip: the table of a call, the DEEP combination of a lane's points
+// for the one-round combine kernel's four points, mpcs_one_round_lane, and the check kernel's one, mpcs_combine_lane<F, K, 1>) and the evaluation at extension points of csrc/deep_kernels.h,
+// compared with a plain `unsigned __int128 % p` restatement in this file: the double sum of the definition and Horner's rule, over
+// the arithmetic of emu_ref.h (which emu_fri.cpp brings in).  Test infrastructure only; never part of the product library.
 //
 //   emu_deep <p> <g> [w]   last line "OK ..." on success; w defaults to g.  Goldilocks runs the Goldilocks policy, its W = 7 form
 //                          when w = 7, AND the Montgomery policy.
@@ -10,7 +11,7 @@
 #undef main
 
 #include "../../ronkathon_amd/csrc/ext2_kernels.h"
-#include "../../ronkathon_amd/csrc/deep_kernels.h"
+#include "../../ronkathon_amd/csrc/mpcs_kernels.h"
 
 // ---------------------------------------------------------------------------------------------------- the restatement
 // G at the point x from the column values there: sum_k sum_c alpha^(k C + c) (col[c] - y[k][c]) / (x - z_k), term by term
@@ -53,6 +54,9 @@ static void run_combine(bool mont, u64 p, u64 g, u64 w) {
     for (u32 C : Cs)
       for (u64 shift : shifts) {
         const u64 N = (u64)1 << n, q = N >> 2, wn = r_pow(g, (p - 1) >> n, p);
+        const u32 mask = mpcs_full_mask(K);
+        MpcsShape sh;
+        CHECK(mpcs_host_shape(K, 1, &C, &mask, &sh) && sh.Y == (u32)K * C, "shape K=%d C=%u refused", K, C);
         Domain D;
         make_domain(D, mont, p, g, shift, n);
         std::vector<u64> M(C * N);
@@ -68,16 +72,18 @@ static void run_combine(bool mont, u64 p, u64 g, u64 w) {
           if (variant == 4) zs[K - 1] = R2{shift % p + (shift % p < ~(u64)0 - p ? p : 0), 0}, want_on = true;   // x_0, maybe as a word >= p
           const R2 alpha{pair_word(p, variant % 5), pair_word(p, (variant * 3 + 1) % 5)};
           // the table
-          std::vector<u64> tab(deep_tab_words(K, C), ~(u64)0), zw(2 * K), yw(2 * (size_t)K * C), aw = {alpha.c0, alpha.c1};
+          std::vector<u64> tab(mpcs_tab_words(1, K, C), ~(u64)0), zw(2 * K), yw(2 * (size_t)K * C), aw = {alpha.c0, alpha.c1};
+          u64 *tab_y = tab.data() + (size_t)MPCS_KW * K, *tab_ap = tab_y + 2 * (size_t)K;
           for (u32 j = 0; j < (u32)K; j++) { zw[j] = zs[j].c0; zw[K + j] = zs[j].c1; }
           for (size_t j = 0; j < ys.size(); j++) { yw[j] = ys[j].c0; yw[ys.size() + j] = ys[j].c1; }
           const E2 a{f.in(aw[0]), f.in(aw[1])};
           int bits = 0;
           census_stage("deep_prep");
-          for (u32 c = 0; c < C; c++) deep_prep_column(x, a, c, tab.data() + (size_t)DEEP_KW * K);
-          for (u32 j = 0; j < (u32)K; j++) bits |= deep_prep_point(x, D.dm, a, zw.data(), yw.data(), K, C, j, tab.data() + (size_t)DEEP_KW * j);
+          for (u32 c = 0; c < C; c++) deep_prep_column(x, a, c, tab_ap);
+          for (u32 j = 0; j < (u32)K; j++) bits |= mpcs_prep_point(x, D.dm, a, zw.data(), sh, j, tab.data() + (size_t)MPCS_KW * j);
+          for (u32 j = 0; j < (u32)K; j++) mpcs_prep_claims(x, a, yw.data(), sh, 0, j, tab_y + 2 * (size_t)j);
           CHECK(bits == (want_on ? 32 : 0), "status K=%d n=%u C=%u variant=%d bits=%d", K, n, C, variant, bits);
-          const DeepTab T{tab.data(), tab.data() + (size_t)DEEP_KW * K};
+          const MpcsTab T{tab.data(), tab_y, tab_ap};
           census_stage(nullptr);
           // the restatement
           std::vector<R2> want(N);
@@ -90,7 +96,7 @@ static void run_combine(bool mont, u64 p, u64 g, u64 w) {
           census_stage("deep_combine");
           for (u64 i = 0; i < q; i++) {
             E2 out[4];
-            deep_combine_lane<F, K, 4>(x, D.dm, T, C, i, [&](u32 c, int t) { return M[c * N + i + (u64)t * q]; }, out);
+            mpcs_one_round_lane<F, K>(x, D.dm, T, sh.C[0], i, [&](u32 c, int t) { return M[c * N + i + (u64)t * q]; }, out);
             for (int t = 0; t < 4; t++)
               CHECK((R2{out[t].c0, out[t].c1} == want[i + t * q]), "combine K=%d n=%u C=%u shift=%llu variant=%d i=%llu t=%d", K, n, C,
                     (unsigned long long)shift, variant, (unsigned long long)i, t);
@@ -99,7 +105,7 @@ static void run_combine(bool mont, u64 p, u64 g, u64 w) {
           census_stage("deep_check");
           for (u64 i = 0; i < N; i += (n == 6 ? 5 : 1)) {
             E2 out[1];
-            deep_combine_lane<F, K, 1>(x, D.dm, T, C, i, [&](u32 c, int) { return M[c * N + i]; }, out);
+            mpcs_combine_lane<F, K, 1>(x, D.dm, T, sh, i, [&](u32, u32 c, int) { return M[c * N + i]; }, out);
             CHECK((R2{out[0].c0, out[0].c1} == want[i]), "check K=%d n=%u C=%u variant=%d i=%llu", K, n, C, variant, (unsigned long long)i);
           }
         }

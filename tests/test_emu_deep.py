@@ -1,4 +1,5 @@
-"""The bodies of csrc/deep_kernels.h compiled for the host (tests/emu/emu_deep.cpp) against the plain `unsigned __int128 % p`
+"""The bodies that ronk_pcs_* runs (csrc/deep_kernels.h and the one-round case of csrc/mpcs_kernels.h) compiled for the host
+(tests/emu/emu_deep.cpp) against the plain `unsigned __int128 % p`
 restatement in the same file: the table of a call, the DEEP combination as the combine kernel's lanes (four points) and as the
 check kernel's lanes (one point) compute it, the on-domain status bit and the zero-inverse convention, and the evaluation at
 extension points, for K = 1, 2, 3, 8 points.  Goldilocks runs its own arithmetic (and the W = 7 form when W = 7) and the Montgomery
@@ -23,8 +24,8 @@ def emu():
     src = os.path.join(ROOT, "tests", "emu", "emu_deep.cpp")
     deps = [src, os.path.join(ROOT, "tests", "emu", "emu_fri.cpp"), os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp"),
             os.path.join(ROOT, "tests", "emu", "emu_ref.h")]
-    deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("deep_kernels.h", "ext2_kernels.h", "ext2.h", "fri_kernels.h",
-                                                                     "field_policy.h", "gl64.h", "mont64.h")]
+    deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("deep_kernels.h", "mpcs_kernels.h", "ext2_kernels.h", "ext2.h",
+                                                                     "fri_kernels.h", "field_policy.h", "gl64.h", "mont64.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         tmp = "%s.tmp.%d" % (exe, os.getpid())   # pytest-xdist workers may rebuild at once
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", tmp, src])
@@ -39,8 +40,8 @@ def emu_device_form(emu):
     src = os.path.join(ROOT, "tests", "emu", "emu_deep.cpp")
     deps = [os.path.join(ROOT, "tests", "emu", "emu_fri.cpp"), os.path.join(ROOT, "tests", "emu", "emu_poseidon.cpp"),
             os.path.join(ROOT, "tests", "emu", "emu_ref.h")]
-    deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("deep_kernels.h", "ext2_kernels.h", "ext2.h", "fri_kernels.h",
-                                                                     "field_policy.h", "gl64.h", "mont64.h")]
+    deps += [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("deep_kernels.h", "mpcs_kernels.h", "ext2_kernels.h", "ext2.h",
+                                                                     "fri_kernels.h", "field_policy.h", "gl64.h", "mont64.h")]
     return emu_cxx.build_device_form(os.path.join(ROOT, "build", "emu_deep_clang"), [src], deps)
 
 

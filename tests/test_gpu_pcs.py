@@ -165,6 +165,13 @@ def test_combine_prime_classes(torch, p, eta):
     check_combine(torch, p, eta, {eta + 1: corners, 9: corners})
 
 
+@pytest.mark.parametrize("p", [PR.GOLDILOCKS, CLASS_FIELDS[0]])
+def test_combine_four_and_eight_points(torch, p):
+    """the larger instantiations of the point count, which the cases above (K <= 3) do not reach: one lane with one column at
+    eight points and five columns at four, and four workgroups over both levels of the point table at eight points with s = g"""
+    check_combine(torch, p, 1, {2: [(1, 8, 1), (5, 4, GEN[p])], 12: [(3, 8, GEN[p])]})
+
+
 def test_goldilocks_with_another_w(torch):
     """W = 7 over Goldilocks has a product with W of its own; another non-residue takes the ordinary product"""
     p = PR.GOLDILOCKS
