@@ -332,6 +332,14 @@ int ronk_curve_msm(const ronk_curve* curve, const uint64_t* points, size_t n_poi
 int ronk_msm_bn254(const uint64_t* points, const uint64_t* scalars, size_t n, uint64_t out[8]);
 int ronk_msm_bn254_dev(const uint64_t* d_points, const uint64_t* d_scalars, size_t n, uint64_t out[8], void* stream);
 
+/* TEST HOOK, not a stable API: one function of the BN254 base-field / G1 arithmetic under the MSM kernels applied on the
+ * device to n elements, raw limbs in, raw limbs out, no form conversion (Montgomery form, any representative in
+ * [0, 2p), exactly as the kernels hold them).  op codes and element sizes: csrc/bn254_probe.h -- field operands and
+ * results are 4 words, predicates write 1 word, an XYZZ point is 16 words (X, Y, ZZ, ZZZ), an affine operand 8.  d_b may
+ * be NULL where the op is unary.  Asynchronous on `stream`; RONK_ERR_INVALID for an unknown op or a null pointer; n = 0
+ * is a no-op. */
+int ronk_bn254_probe_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n, void* stream);
+
 /* kzg::open on the same curve (src/kzg/setup.rs:63-78): `poly.div([-eval_point, ONE])` over the SCALAR field of BN254,
  * r = 21888242871839275222246405745257275088548364400416034343698204186575808495617, then `commit(quotient, g1_srs)`.
  * coeffs: n x 4 words (4 x 64-bit little-endian limbs, standard form; taken mod r), ascending degree.  z: 4 words.

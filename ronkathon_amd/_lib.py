@@ -115,6 +115,7 @@ _SIG = {
     "ronk_curve_msm": (_int, [_vp, _vp, _sz, _vp, _sz, _vp]),
     "ronk_msm_bn254": (_int, [_vp, _vp, _sz, _vp]),
     "ronk_msm_bn254_dev": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "ronk_bn254_probe_dev": (_int, [_int, _vp, _vp, _vp, _sz, _vp]),   # test hook (csrc/bn254_probe.h)
     "ronk_poly_div_linear_bn254_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
     "ronk_kzg_open_bn254_dev": (_int, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ronk_kzg_open_bn254": (_int, [_vp, _sz, _vp, _vp, _sz, _vp, _vp]),

@@ -4,6 +4,7 @@
 #include "runtime.h"
 #include "msm_kernels.h"
 #include "fr_scan_kernels.h"
+#include "bn254_probe.h"
 
 namespace {
 
@@ -183,6 +184,38 @@ extern "C" int ronk_msm_bn254(const uint64_t* points, const uint64_t* scalars, s
   const u64 *dp = hc.in(points, 8 * n), *ds = hc.in(scalars, 4 * n);
   RCHK(hc.rc);
   return ronk_msm_bn254_dev(dp, ds, n, out, nullptr);
+}
+
+// ------------------------------------------------------------------------------ test hook: bn254.h on raw limbs, on the device
+namespace {
+// one lane per element, grid-stride; OP is a compile-time constant so that every instantiation holds one function of
+// bn254.h as the MSM kernels inline it (one kernel with a run-time switch would put every function, four whole XYZZ
+// additions among them, into one body and change their register allocation).  The price is carried by the product
+// library for a test hook: 15 instantiations, about 0.28 MB more in this file's object (1.01 -> 1.29 MB) and about a
+// third more time to compile it; nothing on the MSM's own path calls or shares code with them.
+template <int OP>
+__global__ void __launch_bounds__(256) bn254_probe_kernel(const u64* a, const u64* b, u64* out, size_t n) {
+  const bn254::ProbeShape ps = bn254::probe_shape(OP);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    bn254::probe_apply<OP>(a + i * ps.wa, b + i * ps.wb, out + i * ps.wo);
+}
+}  // namespace
+
+// out[i] = op(a[i], b[i]) for one function of csrc/bn254.h (codes and element sizes: csrc/bn254_probe.h), raw limbs in,
+// raw limbs out.  d_b may be NULL for the unary ops.  Asynchronous on `stream`.
+extern "C" int ronk_bn254_probe_dev(int op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, size_t n, void* stream) {
+  const bn254::ProbeShape ps = bn254::probe_shape(op);
+  if (ps.wo == 0) return RONK_ERR_INVALID;
+  if (n == 0) return RONK_OK;
+  if (!d_a || !d_out || (ps.wb && !d_b)) return RONK_ERR_INVALID;
+  RCHK(need_device());
+  const u32 blocks = (u32)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+#define RONK_PROBE_LAUNCH(OP) \
+  hipLaunchKernelGGL((bn254_probe_kernel<OP>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_a, d_b, d_out, n)
+  BN254_PROBE_DISPATCH(op, RONK_PROBE_LAUNCH)
+#undef RONK_PROBE_LAUNCH
+  HIPCHK(hipGetLastError());
+  return RONK_OK;
 }
 
 // ------------------------------------------------------------------------------ kzg::open over BN254 (src/kzg/setup.rs:63-78)

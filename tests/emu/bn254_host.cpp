@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "../../ronkathon_amd/csrc/bn254.h"
+#include "../../ronkathon_amd/csrc/bn254_probe.h"
 #include "../../ronkathon_amd/csrc/bn254_fr.h"
 #include "../../ronkathon_amd/csrc/msm_common.h"
 
@@ -51,6 +52,16 @@ void h_point_op(const u64* p, const u64* q, int neg_q, int mode, u64* out) {
     acc = xyzz_dbl(acc);
   }
   xyzz_store_affine(acc, out);
+}
+// the host twin of ronk_bn254_probe_dev: out[i] = op(a[i], b[i]) on RAW limbs (csrc/bn254_probe.h: same op codes, same
+// element sizes, same per-element body -- here over the __int128 fallback of acc_mad).  Returns 0, or -1 for an unknown op.
+int h_raw_op(int op, const u64* a, const u64* b, u64* out, size_t n) {
+  const ProbeShape ps = probe_shape(op);
+  if (ps.wo == 0) return -1;
+#define H_RAW_RUN(OP) for (size_t i = 0; i < n; i++) probe_apply<OP>(a + i * ps.wa, b + i * ps.wb, out + i * ps.wo)
+  BN254_PROBE_DISPATCH(op, H_RAW_RUN)
+#undef H_RAW_RUN
+  return 0;
 }
 // k * p by double-and-add on XYZZ (k: 4 x u64)
 void h_scalar_mul(const u64* p, const u64* k, u64* out) {

@@ -15,7 +15,7 @@ SO = os.path.join(ROOT, "build", "libbn254_host.so")
 @pytest.fixture(scope="module")
 def H():
     src = os.path.join(ROOT, "tests", "emu", "bn254_host.cpp")
-    deps = [src] + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("bn254.h", "bn254_fr.h", "bn254_consts.h", "msm_common.h")]
+    deps = [src] + [os.path.join(ROOT, "ronkathon_amd", "csrc", f) for f in ("bn254.h", "bn254_probe.h", "bn254_fr.h", "bn254_consts.h", "msm_common.h")]
     os.makedirs(os.path.dirname(SO), exist_ok=True)
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", SO, src])
